@@ -4,7 +4,7 @@
 around the ``train``-equivalent with validation off (:222-249), benchmark-default hyper-parameters
 (gamma 0.99, lr Exp(0.1 -> 1e-5, 0.995), epsilon Exp(1.0 -> 0.01, 0.995), :53-59).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--agents A]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--agents A] [--dump-outputs DIR]
 
 One "step" = one vector step of the fused loop (select -> env.step -> learn for every agent).
 N > 1: one rank per GPU; every GPU owns its own agents and a table replica and exchanges Q-deltas every
@@ -13,6 +13,9 @@ N > 1: one rank per GPU; every GPU owns its own agents and a table replica and e
 environment) or, when bench.py is run plainly with ``--gpus N``, by bench.py itself as child processes
 (like the reference's harness starts its own ranks, throughput_benchmark.py:326-366).  Rank 0 prints ONE
 JSON line.
+
+``--dump-outputs DIR`` writes what the K timed steps computed (rank 0's view: the Q-table, the episode returns and
+the environment state ``run_steps`` hands back) as ``DIR/<name>.npy``; see :func:`dump_outputs`.
 """
 
 from __future__ import annotations
@@ -25,6 +28,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -48,6 +52,9 @@ WORKLOADS = {
 PUBLISHED_TICTACTOE_SINGLE_THREAD_128 = 22_300.0  # benchmark_results/single_thread_128_agents.json
 SYNC_EVERY = 100  # BASELINE.json configs[3]: all-reduce of Q-deltas every 100 steps
 ROOFLINE_SAMPLES = 8  # further launches of the same K steps, bracketed by HIP events
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together, .npy headers included
+DUMP_ARRAY_BYTES = 4_000_000  # --dump-outputs: any one output other than the Q-table
+NPY_HEADER_BYTES = 4096  # an upper bound of one .npy header
 
 
 def algorithmic_bytes_per_env_step(actions: int, masked: bool, esize: int = 4) -> int:
@@ -118,6 +125,51 @@ def cpu_baseline(wl, budget_s: float = 12.0):
     return out
 
 
+def _dump_sample(name, arr, budget):
+    """``arr`` (float32 stays float32, everything else becomes float64: int32 / uint32 / uint8 exactly) if it fits
+    ``budget`` bytes, else a sample of its rows, drawn without replacement by a generator seeded from ``name`` alone
+    (the same rows for the same shape, whatever build runs) and returned with their indices."""
+    arr = np.asarray(arr)
+    arr = arr.astype(np.float32 if arr.dtype == np.float32 else np.float64, copy=False)
+    if arr.nbytes <= budget or arr.ndim == 0:
+        return arr, None
+    row_bytes = arr.nbytes // arr.shape[0] + 8  # + its index (float64)
+    k = max(1, budget // row_bytes)
+    rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(arr.shape[0], k, replace=False))
+    return arr[rows], rows.astype(np.float64)
+
+
+def dump_outputs(out_dir, result, q_table) -> list:
+    """What a caller of the timed path received from its last call: ``result`` = the ``(average return, episode
+    returns, env, state dict)`` of ``run_steps``, ``q_table`` = the table it trained.  One ``.npy`` per array;
+    an output larger than its share of ``DUMP_MAX_BYTES`` is replaced by a fixed sample of its rows and
+    ``<name>_rows.npy`` (the row indices).  Returns the names of the files written."""
+    avg, returns, _env, sd = result
+    states = sd["states"]
+    outputs = {
+        "avg_return": np.float64(avg),
+        "episode_returns": np.asarray(returns, dtype=np.float32),  # float32 values (widened to Python floats)
+        **({f"states_{k}": v for k, v in states.items()} if isinstance(states, dict) else {"states": states}),
+        "agent_returns": sd["rewards"],
+        "env_aux": sd["aux"],
+        "rng_step": np.float64(sd["rng_step"]),
+        "lr": np.float64(sd["lr"]),
+        "exploration_rate": np.float64(sd["exploration_rate"]),
+    }
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written, used = [], 0
+    for name, arr in [*outputs.items(), ("q_table", q_table)]:
+        budget = (DUMP_MAX_BYTES - used if name == "q_table" else DUMP_ARRAY_BYTES) - 2 * NPY_HEADER_BYTES
+        data, rows = _dump_sample(name, arr, budget)
+        for fname, a in ((name, data), (f"{name}_rows", rows)):
+            if a is not None:
+                np.save(out_dir / f"{fname}.npy", a)
+                used += a.nbytes + NPY_HEADER_BYTES
+                written.append(f"{fname}.npy")
+    return written
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks as child processes (the parent never
     touches a GPU) and pass their one JSON line through."""
@@ -155,7 +207,12 @@ def main() -> None:
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the ranks; gloo + fewer GPUs than ranks (ranks then share GPUs) is a "
                          "rehearsal of the N > 1 path on a small box, not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (Q-table, episode returns, environment state) as "
+                         "DIR/<name>.npy, at most 64 MB in all (a fixed sample of rows of larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "RANK" in os.environ  # started by torch.distributed.run (also with a single rank)
     if args.gpus > 1 and not launched:
@@ -242,11 +299,15 @@ def main() -> None:
 
     def run_steps(steps, state):
         """`run_steps`; the reference divides by the number of finished episodes (single_thread_runtime.py:67),
-        so a very short call in which no episode ends raises ZeroDivisionError AFTER all its work is done."""
+        so a very short call in which no episode ends raises ZeroDivisionError AFTER all its work is done (its
+        result is then completed here: no average, no returns)."""
         try:
-            return rt.run_steps(steps, env, state)[3]
+            return rt.run_steps(steps, env, state)
         except ZeroDivisionError:
-            return env.state_dict()
+            sd = env.state_dict()
+            sd.update(episode_rewards=[], rng_step=algo.step_counter, lr=rt.lr_schedule.get_value(),
+                      exploration_rate=rt.exploration_rate_schedule.get_value())
+            return float("nan"), [], env, sd
 
     # Untimed warm-up: W vector steps, taken in a few calls so that every per-call path of the timed call
     # (engine slots, page-locked result block, the Python around them) has run before the clock starts.
@@ -257,10 +318,10 @@ def main() -> None:
     pieces = [w // 4] * 3 + [w - 3 * (w // 4)] if w >= 8 else [1] * w
     sd = None
     for k in pieces:
-        sd = run_steps(k, sd)
+        sd = run_steps(k, sd)[3]
     sync_all()
     t0 = time.perf_counter()
-    sd = run_steps(args.steps, sd)  # EXACTLY K timed vector steps
+    result = run_steps(args.steps, sd)  # EXACTLY K timed vector steps
     t_call = time.perf_counter() - t0
     # the region closes as it opened, with the device drained and a barrier: every rank stops its clock when ITS
     # K steps are complete on the device, the slowest rank's time is the job's (MAX over ranks below) -- the
@@ -269,6 +330,11 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     sync_all()
     stats = dict(rt.last_stats)
+    sd = result[3]
+    if args.dump_outputs and rank == 0:
+        # before the roofline samples below, which continue the training
+        dumped = dump_outputs(args.dump_outputs, result, algo.q_table)
+        sys.stderr.write(f"bench.py: wrote {len(dumped)} arrays to {args.dump_outputs}\n")
     if use_dist:
         import torch
 
@@ -282,7 +348,7 @@ def main() -> None:
     persistent = stats["launches"] < args.steps or args.steps == 1 and n <= 512 and wl["actions"] <= 64
     samples = []
     for _ in range(ROOFLINE_SAMPLES if persistent else 1):
-        sd = run_steps(args.steps, sd)
+        sd = run_steps(args.steps, sd)[3]
         samples.append(dict(rt.last_stats))
     rt.close_training()  # (replicas: the records logged since the last regular exchange, and what is in flight)
     sync_all()
