@@ -20,7 +20,7 @@ LIB_PATH = Path(os.environ.get("QE_LIB_PATH") or Path(__file__).resolve().parent
 ABI_VERSION = 2  # QE_ABI_VERSION of include/qlearn_engine.h
 QE_F32, QE_F64 = 0, 1
 LEARN_ITER, LEARN_VEC = 0, 1
-ENV_HASH, ENV_GRID, ENV_BANDIT, ENV_TICTACTOE = 0, 1, 2, 3
+ENV_HASH, ENV_GRID, ENV_BANDIT, ENV_TICTACTOE, ENV_TABLE = 0, 1, 2, 3, 4
 OPT_ROLLOUT_PATH = 0
 OPT_USE_GRAPH = 1
 OPT_TOKEN_ROUNDS = 2
@@ -81,6 +81,22 @@ class EnvParams(C.Structure):
     ]
 
 
+class TableMdp(C.Structure):
+    """``qe_table_mdp``: host pointers to an encoded finite MDP (``environments.device_envs.encode_table_mdp``)."""
+
+    _fields_ = [
+        ("k", C.c_int32),
+        ("n_start", C.c_int32),
+        ("thr", C.POINTER(C.c_uint32)),
+        ("next_state", C.POINTER(C.c_int32)),
+        ("reward", C.POINTER(C.c_float)),
+        ("terminated", C.POINTER(C.c_uint8)),
+        ("start_thr", C.POINTER(C.c_uint32)),
+        ("start_state", C.POINTER(C.c_int32)),
+        ("masks", C.POINTER(C.c_uint8)),
+    ]
+
+
 class RolloutStats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double),
@@ -129,6 +145,7 @@ PROTOTYPES = {
     "qe_choose_actions": (C.c_int, [_P, _I32P, C.c_int64, _U8P, C.c_double, C.c_int32, _I32P]),
     "qe_learn": (C.c_int, [_P, _I32P, _I32P, _F32P, _I32P, _U8P, C.c_int64, C.c_double, _U8P, C.c_int32]),
     "qe_env_create": (C.c_int, [C.POINTER(_P), _P, C.c_int64, C.POINTER(EnvParams)]),
+    "qe_env_create_table": (C.c_int, [C.POINTER(_P), _P, C.c_int64, C.POINTER(EnvParams), C.POINTER(TableMdp)]),
     "qe_env_destroy": (C.c_int, [_P]),
     "qe_env_reset": (C.c_int, [_P, C.c_int32, C.c_uint32]),
     "qe_env_observe": (C.c_int, [_P, _I32P, _U8P, _F32P]),

@@ -217,7 +217,7 @@ int rollout_begin_impl(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps
     }
     if (sl.inline_sched) { c.thr = nullptr; c.lr = nullptr; }  // in the kernel-argument segment
     c.ep_key = sl.ep_key.p; c.ep_ret = sl.ep_ret.p; c.ep_cap = e->ep_cap;
-    const EnvCtx ev = make_envctx(e, &env->p, nullptr, 0);
+    const EnvCtx ev = make_envctx(e, env);
     if (trace_host) {
         HIP_TRY(e->trace.ensure((size_t)(steps * env->N)));
         c.trace = e->trace.p;
@@ -239,7 +239,7 @@ int rollout_begin_impl(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps
     // turnstile path: one launch per step, all workgroups resident, rows handed from agent to agent
     bool turn = false;
     if (learn && !persistent && (e->opt_path == 4 || (e->opt_path == 0 && TURN_AUTO))) {
-        int& per_cu = e->turn_blocks_per_cu[env->p.kind & 3];
+        int& per_cu = e->turn_blocks_per_cu[env->p.kind];
         if (per_cu == 0) {
             per_cu = turn_occupancy<T, Env>(e);
             if (per_cu <= 0) per_cu = -1;  // (asked once; without an answer the path is not taken)
@@ -539,6 +539,7 @@ int rollout_begin_dispatch(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t s
         case QE_ENV_GRID: return rollout_begin_impl<T, GridEnv>(e, env, sl, steps, mode, learn, trace);
         case QE_ENV_BANDIT: return rollout_begin_impl<T, BanditEnv>(e, env, sl, steps, mode, learn, trace);
         case QE_ENV_TICTACTOE: return rollout_begin_impl<T, TttEnv>(e, env, sl, steps, mode, learn, trace);
+        case QE_ENV_TABLE: return rollout_begin_impl<T, TableEnv>(e, env, sl, steps, mode, learn, trace);
     }
     return qe_fail(QE_ERR_INVALID, "unknown env kind %d", env->p.kind);
 }
@@ -550,6 +551,7 @@ int by_kind(int kind, F f) {
         case QE_ENV_GRID: return f(GridEnv{});
         case QE_ENV_BANDIT: return f(BanditEnv{});
         case QE_ENV_TICTACTOE: return f(TttEnv{});
+        case QE_ENV_TABLE: return f(TableEnv{});
     }
     return qe_fail(QE_ERR_INVALID, "unknown env kind %d", kind);
 }
@@ -957,6 +959,8 @@ int qe_learn(qe_engine* e, const int32_t* states, const int32_t* actions, const 
 }
 
 // ---- environments ------------------------------------------------------------------------------
+static int env_alloc(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p);
+
 int qe_env_create(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p) {
     if (!out || !e || !p || N <= 0) return qe_fail(QE_ERR_INVALID, "bad argument");
     *out = nullptr;
@@ -977,9 +981,82 @@ int qe_env_create(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p)
             if (e->S != 19683 || e->A != 9)
                 return qe_fail(QE_ERR_INVALID, "TicTacToe needs state_size 19683 (3^9) and action_size 9");
             break;
+        case QE_ENV_TABLE: return qe_fail(QE_ERR_INVALID, "table environments are created with qe_env_create_table");
         default: return qe_fail(QE_ERR_INVALID, "unknown env kind %d", p->kind);
     }
     HIP_TRY(hipSetDevice(e->device));
+    qe_env* env = nullptr;
+    if (int rc = env_alloc(&env, e, N, p)) return rc;
+    *out = env;
+    return qe_env_reset(env, 0, 0);
+}
+
+int qe_env_create_table(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p, const qe_table_mdp* t) {
+    if (!out || !e || !p || !t || N <= 0) return qe_fail(QE_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    if (e->ld > 256) return qe_fail(QE_ERR_UNSUPPORTED, "device environments support action_size <= 256");
+    if (p->kind != QE_ENV_TABLE) return qe_fail(QE_ERR_INVALID, "qe_env_create_table needs kind QE_ENV_TABLE");
+    if (t->k < 1 || t->k > 8) return qe_fail(QE_ERR_INVALID, "k = %d outcome slots: must be 1 .. 8", (int)t->k);
+    if (t->n_start < 1 || t->n_start > e->S) return qe_fail(QE_ERR_INVALID, "n_start = %d: must be 1 .. state_size", (int)t->n_start);
+    if (!t->thr || !t->next_state || !t->reward || !t->terminated || !t->start_thr || !t->start_state)
+        return qe_fail(QE_ERR_INVALID, "table arrays must not be NULL (masks may)");
+    const uint64_t cells = (uint64_t)e->S * (uint64_t)e->A, recs = cells * (uint64_t)t->k;
+    if (recs > 0x80000000ull) return qe_fail(QE_ERR_INVALID, "state_size * action_size * k = %llu outcome records: at most 2^31",
+                                             (unsigned long long)recs);
+    for (uint64_t j = 0; j < recs; ++j)
+        if (t->next_state[j] < 0 || t->next_state[j] >= e->S)
+            return qe_fail(QE_ERR_INDEX, "next_state[%llu] = %d is out of range [0, %lld)", (unsigned long long)j,
+                           (int)t->next_state[j], (long long)e->S);
+    for (int j = 0; j < t->n_start; ++j) {
+        if (t->start_state[j] < 0 || t->start_state[j] >= e->S)
+            return qe_fail(QE_ERR_INDEX, "start_state[%d] = %d is out of range [0, %lld)", j, (int)t->start_state[j],
+                           (long long)e->S);
+        if (j > 0 && t->start_thr[j] < t->start_thr[j - 1])
+            return qe_fail(QE_ERR_INVALID, "start_thr must be non-decreasing (entry %d)", j);
+    }
+    // one 16-byte record {thr, next, reward bits, terminated} per outcome slot; slot k - 1 is the fallback, so its
+    // threshold is never the reason a search stops short of it
+    std::vector<uint32_t> rec((size_t)recs * 4);
+    for (uint64_t j = 0; j < recs; ++j) {
+        uint32_t rbits;
+        memcpy(&rbits, &t->reward[j], 4);
+        const bool last = (int)(j % (uint64_t)t->k) == t->k - 1;
+        rec[4 * j] = last ? 0xFFFFFFFFu : t->thr[j];
+        rec[4 * j + 1] = (uint32_t)t->next_state[j];
+        rec[4 * j + 2] = rbits;
+        rec[4 * j + 3] = t->terminated[j] ? 1u : 0u;
+    }
+    std::vector<uint32_t> start((size_t)t->n_start * 2);
+    for (int j = 0; j < t->n_start; ++j) { start[2 * j] = t->start_thr[j]; start[2 * j + 1] = (uint32_t)t->start_state[j]; }
+    std::vector<uint32_t> maskw;
+    if (t->masks) pack_masks(t->masks, e->S, e->A, maskw);
+    HIP_TRY(hipSetDevice(e->device));
+    qe_env_params q = *p;
+    q.masked = t->masks ? 1 : 0;
+    qe_env* env = nullptr;
+    if (int rc = env_alloc(&env, e, N, &q)) return rc;
+    env->tbl_k = t->k;
+    env->tbl_n_start = t->n_start;
+    hipError_t err = env->tbl_rec.ensure(rec.size());
+    if (err == hipSuccess) err = env->tbl_start.ensure(start.size());
+    if (err == hipSuccess && t->masks) err = env->tbl_mask.ensure(maskw.size());
+    if (err != hipSuccess) {
+        qe_env_destroy(env);
+        return qe_fail(QE_ERR_OOM, "table allocation failed: %s", hipGetErrorString(err));
+    }
+    err = hipMemcpy(env->tbl_rec.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(env->tbl_start.p, start.data(), start.size() * 4, hipMemcpyHostToDevice);
+    if (err == hipSuccess && t->masks) err = hipMemcpy(env->tbl_mask.p, maskw.data(), maskw.size() * 4, hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        qe_env_destroy(env);
+        return qe_fail(QE_ERR_NO_DEVICE, "table upload failed: %s", hipGetErrorString(err));
+    }
+    *out = env;
+    return qe_env_reset(env, 0, 0);
+}
+
+// The per-agent device state of an environment (no reset yet).
+static int env_alloc(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p) {
     qe_env* env = new qe_env();
     env->e = e; env->p = *p; env->N = N;
     const size_t un = (size_t)N;
@@ -1008,7 +1085,7 @@ int qe_env_create(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p)
         return qe_fail(QE_ERR_OOM, "env allocation failed: %s", hipGetErrorString(err));
     }
     *out = env;
-    return qe_env_reset(env, 0, 0);
+    return QE_OK;
 }
 
 int qe_env_destroy(qe_env* env) {
@@ -1018,6 +1095,7 @@ int qe_env_destroy(qe_env* env) {
     env->s.release(); env->a.release(); env->n.release(); env->list.release(); env->pend_list.release(); env->r.release();
     env->acc.release(); env->term.release(); env->pred.release(); env->aux.release();
     env->bitmap.release(); env->adv_bitmap.release(); env->turn_next.release(); env->masks.release(); env->vinc.release();
+    env->tbl_rec.release(); env->tbl_start.release(); env->tbl_mask.release();
     delete env;
     return QE_OK;
 }
@@ -1029,7 +1107,7 @@ int qe_env_reset(qe_env* env, int32_t has_seed, uint32_t seed) {
     HIP_TRY(hipSetDevice(e->device));
     env_touched(env);
     if (has_seed) env->p.seed = seed;
-    const EnvCtx ev = make_envctx(e, &env->p, nullptr, 0);
+    const EnvCtx ev = make_envctx(e, env);
     int rc = by_kind(env->p.kind, [&](auto tag) {
         using Env = decltype(tag);
         hipLaunchKernelGGL(k_env_reset<Env>, dim3(grid_for(env->N, 256)), dim3(256), 0, e->stream, ev,
@@ -1055,7 +1133,7 @@ int qe_env_observe(qe_env* env, int32_t* obs, uint8_t* masks, float* agent_rewar
     if (masks) {
         const size_t bytes = (size_t)env->N * e->A;
         HIP_TRY(env->masks.ensure(bytes));
-        const EnvCtx ev = make_envctx(e, &env->p, nullptr, 0);
+        const EnvCtx ev = make_envctx(e, env);
         const int nsub = (e->A + 3) / 4;
         int rc = by_kind(env->p.kind, [&](auto tag) {
             using Env = decltype(tag);
@@ -1103,7 +1181,7 @@ int qe_env_step(qe_env* env, const int32_t* actions, int32_t* obs, float* reward
     HIP_TRY(hipSetDevice(e->device));
     env_touched(env);
     HIP_TRY(hipMemcpyAsync(env->a.p, actions, env->N * 4, hipMemcpyHostToDevice, e->stream));
-    const EnvCtx ev = make_envctx(e, &env->p, nullptr, 0);
+    const EnvCtx ev = make_envctx(e, env);
     int rc = by_kind(env->p.kind, [&](auto tag) {
         using Env = decltype(tag);
         hipLaunchKernelGGL(k_env_step<Env>, dim3(grid_for(env->N, 256)), dim3(256), 0, e->stream, ev, env->N,

@@ -24,6 +24,12 @@ struct EnvCtx {
     int32_t A, n_words;
     // host-provided masks (HostEnv): packed bits, n_words uint32 per agent
     const uint32_t* maskbits;
+    // TableEnv (appended: the fields above keep their offsets): tbl_k 16-byte outcome records per (state, action),
+    // the start support as {thr, state} pairs, per-state mask words (n_words uint32 per state) or null
+    const uint4* tbl_rec;
+    const uint2* tbl_start;
+    const uint32_t* tbl_mask;
+    int32_t tbl_k, tbl_n_start;
 };
 
 struct Transition {
@@ -239,6 +245,65 @@ struct TttEnv {
     static __device__ __forceinline__ int32_t reset(const EnvCtx& ev, int64_t agent, uint32_t& aux) {
         aux = begin_episode(word0(ev, agent, TTT_RESET_STEP));
         return encode(aux & 0x1FFu, 0u);
+    }
+};
+
+// ---- TableEnv: a finite MDP given as arrays in HBM (environments/device_envs.py:TabularMDPEnv) ----------------------
+// Per (state, action) tbl_k records {thr, next, reward bits, terminated}, outcome k of the encoded list in record k; the
+// last outcome and the padding records behind it (copies of it) carry thr = 2^32 - 1.  The outcome is the first record
+// with u < thr, else the last record: the encoding's "first k with u < thr_k, else the last outcome".  A deterministic
+// step (tbl_k == 1) is one 16-byte load, a stochastic one walks the records until it stops.  The start state is the
+// same search, by bisection, over the support's thresholds.
+// Draw word: TttEnv::word0 with C_TABLE, so that resuming and sharding work as for TicTacToe; aux stays 0.
+constexpr uint32_t C_TABLE = 0x3C6EF372u;
+constexpr uint32_t C_TABLE_STEP = 0x27D4EB2Fu;
+constexpr uint32_t C_TABLE_START = 0x165667B1u;
+
+struct TableEnv {
+    // two agents that take the same action in the same state in one step see the same reward, termination flag
+    // and (unless it terminates) successor: outcomes are drawn per agent and step
+    static constexpr bool kSameOutcome = false;
+    static __device__ __forceinline__ uint32_t word0(const EnvCtx& ev, int64_t agent, unsigned long long step) {
+        const uint32_t inner = mix32((ev.agent_offset + (uint32_t)agent) ^ (ev.seed ^ C_TABLE));
+        return mix32(inner + (uint32_t)step * 0x9E3779B9u + (uint32_t)(step >> 32));
+    }
+    static __device__ __forceinline__ int32_t start_state(const EnvCtx& ev, uint32_t u) {
+        int lo = 0, hi = ev.tbl_n_start - 1;  // first entry below the last with u < thr, else the last
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (u < ev.tbl_start[mid].x) hi = mid; else lo = mid + 1;
+        }
+        return (int32_t)ev.tbl_start[lo].y;
+    }
+    static __device__ __forceinline__ uint32_t valid4(const EnvCtx& ev, int64_t, int32_t obs, int sub) {
+        if (!ev.masked) return in_range4(sub, ev.A);
+        const uint32_t* w = ev.tbl_mask + (uint32_t)obs * (uint32_t)ev.n_words;
+        return valid4_from_words([&](int k) { return w[k]; }, sub, ev.A);
+    }
+    static __device__ __forceinline__ Transition step(const EnvCtx& ev, int64_t agent, int32_t obs,
+                                                      uint32_t&, int32_t action, unsigned long long step) {
+        const uint4* r = ev.tbl_rec + ((uint32_t)obs * (uint32_t)ev.A + (uint32_t)action) * (uint32_t)ev.tbl_k;
+        uint4 rec = r[0];
+        uint32_t h0 = 0u;
+        if (ev.tbl_k > 1) {
+            h0 = word0(ev, agent, step);
+            const uint32_t u = mix32(h0 ^ C_TABLE_STEP);
+            for (int k = 1; k < ev.tbl_k && u >= rec.x; ++k) rec = r[k];
+        }
+        Transition t;
+        t.reward = __uint_as_float(rec.z);
+        t.terminated = rec.w != 0u;
+        if (t.terminated) {
+            if (ev.tbl_k == 1) h0 = word0(ev, agent, step);
+            t.next_obs = start_state(ev, mix32(h0 ^ C_TABLE_START));
+        } else {
+            t.next_obs = (int32_t)rec.y;
+        }
+        return t;
+    }
+    static __device__ __forceinline__ int32_t reset(const EnvCtx& ev, int64_t agent, uint32_t& aux) {
+        aux = 0u;
+        return start_state(ev, mix32(word0(ev, agent, TTT_RESET_STEP) ^ C_TABLE_START));
     }
 };
 

@@ -159,7 +159,7 @@ struct qe_engine {
     unsigned long long turn_epoch = 1;  // turnstile path: record tag of the next call's step 0 (0 = a cleared record)
     DevBuf<TurnRow> turn_rows;          // turnstile path: [S][2] touchers of a row per step parity, allocated on first use
     bool turn_no_memory = false;        // ... that allocation failed: the path is not taken by this engine
-    int turn_blocks_per_cu[4] = {0, 0, 0, 0};  // resident workgroups of k_step_turn per CU, by environment kind (0: not yet asked)
+    int turn_blocks_per_cu[5] = {0, 0, 0, 0, 0};  // resident workgroups of k_step_turn per CU, by environment kind (0: not yet asked)
     hipStream_t debug_stream = nullptr;        // qe_debug_occupy_cus
     int opt_graph = 1; // QE_OPT_USE_GRAPH
     int opt_rounds = 0; // QE_OPT_TOKEN_ROUNDS (0 = automatic)
@@ -240,6 +240,9 @@ struct qe_env {
     DevBuf<uint32_t> aux, bitmap, adv_bitmap;
     DevBuf<uint32_t> turn_next;            // turnstile path: [2][N][2] overflow-list links, allocated on first use
     DevBuf<double> vinc;
+    // QE_ENV_TABLE: outcome records (4 words each), start support ({thr, state} pairs), per-state mask words
+    DevBuf<uint32_t> tbl_rec, tbl_start, tbl_mask;
+    int32_t tbl_k = 0, tbl_n_start = 0;
     // host copy of (observations, env-internal state, running returns) left by the latest rollout's
     // result block; valid until anything else changes the device state
     const int32_t* mirror_obs = nullptr;
@@ -258,6 +261,19 @@ inline EnvCtx make_envctx(const qe_engine* e, const qe_env_params* p, const uint
         ev.side = p->side; ev.episode_len = p->episode_len; ev.agent_offset = p->agent_offset;
     } else {
         ev.kind = -1; ev.masked = masked;
+    }
+    return ev;
+}
+
+// The parameters of a device environment's kernels (make_envctx + the table of a QE_ENV_TABLE environment).
+inline EnvCtx make_envctx(const qe_engine* e, const qe_env* env) {
+    EnvCtx ev = make_envctx(e, &env->p, nullptr, 0);
+    if (env->p.kind == QE_ENV_TABLE) {
+        ev.tbl_rec = (const uint4*)env->tbl_rec.p;
+        ev.tbl_start = (const uint2*)env->tbl_start.p;
+        ev.tbl_mask = env->tbl_mask.p;
+        ev.tbl_k = env->tbl_k;
+        ev.tbl_n_start = env->tbl_n_start;
     }
     return ev;
 }

@@ -4,7 +4,7 @@
 #include "qe_rollout_df.h"
 
 #if !defined(QE_INST_T) || !defined(QE_INST_ENV)
-#error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv>"
+#error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
 #endif
 
 // Which build ran is reported to the caller (qe_rollout_stats::kernel_variant, see qe_variant_bits in the header).
@@ -85,7 +85,7 @@ int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& 
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    if constexpr (std::is_same<Env, HashEnv>::value) {
+    if constexpr (std::is_same<Env, HashEnv>::value || std::is_same<Env, TableEnv>::value) {  // any A, masked or not
         auto by_mask = [&](auto nv) { if (env->p.masked) go(nv, Yes{}); else go(nv, No{}); };
         switch (e->ld) {  // a power of two (row_stride)
             case 4: by_mask(std::integral_constant<int, 1>{}); break;

@@ -4,7 +4,7 @@
 #include "qe_host.h"
 
 #if !defined(QE_INST_T) || !defined(QE_INST_ENV)
-#error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv>"
+#error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
 #endif
 
 template <typename T, class Env, int LC = 0>

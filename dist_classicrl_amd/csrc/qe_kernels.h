@@ -1215,7 +1215,13 @@ __global__ __launch_bounds__(FAST_BLOCK) void k_eval(Ctx<T> c, EnvCtx ev, long l
         const U4 x = philox4x32_10(c.agent_offset + (uint32_t)i, (uint32_t)step, (uint32_t)(step >> 32),
                                    STREAM_POLICY, c.seed_lo, c.seed_hi);
         T picked;
-        const int act = select_action(row, Env::valid4(ev, i, n, sub), sub, c.L, false, x.y, x.z, &picked, c.nan_select != 0);
+        int act = select_action(row, Env::valid4(ev, i, n, sub), sub, c.L, false, x.y, x.z, &picked, c.nan_select != 0);
+        if (act < 0) {
+            // No selectable action (every action masked, or a NaN row maximum): reported as the rollout kernels do
+            // (advance_with_draws); action 0 keeps the step inside the environment's tables.
+            if (sub == 0) c.ctrl->error = ERR_EMPTY_CHOICE;
+            act = 0;
+        }
         const Transition tr = Env::step(ev, i, n, aux, act, step);  // computed redundantly by every lane
         acc += tr.reward;
         if (tr.terminated) {

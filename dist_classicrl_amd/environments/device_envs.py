@@ -15,6 +15,7 @@ path: ``GpuRolloutQLearning.run_steps`` keeps select -> env.step -> learn on the
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -66,10 +67,13 @@ class DeviceVecEnv:
         self._resident = None
         self._chunk_limits = {}
         self._lib = _lib.load()
-        _lib.check(self._lib.qe_env_create(C.byref(self._h), algorithm.handle, self.num_agents,
-                                           C.byref(self._params)))
+        self._create(algorithm)
         self._algo = algorithm
         return self
+
+    def _create(self, algorithm) -> None:
+        _lib.check(self._lib.qe_env_create(C.byref(self._h), algorithm.handle, self.num_agents,
+                                           C.byref(self._params)))
 
     def _need(self):
         if not self._h.value:
@@ -227,3 +231,241 @@ class TicTacToeEnv(DeviceVecEnv):
     def __init__(self, num_agents, seed=1, agent_offset=0):
         p = _lib.EnvParams(kind=self.kind, masked=1, seed=int(seed) & 0xFFFFFFFF, agent_offset=int(agent_offset))
         super().__init__(num_agents, 19683, 9, p)
+
+
+# ---- finite MDPs given as tables ------------------------------------------------------------------------------------
+MAX_OUTCOMES = 8  # outcome slots per (state, action) the device environment supports
+_TWO32 = 4294967296.0
+
+
+class TableMDP(NamedTuple):
+    """A finite MDP in the form the device environment stores (see :func:`encode_table_mdp`)."""
+
+    thr: np.ndarray          # uint32[S, A, K]  sampling thresholds; 2**32 - 1 from the last outcome on
+    next_state: np.ndarray   # int32[S, A, K]   (slots behind the last outcome repeat it)
+    reward: np.ndarray       # float32[S, A, K]
+    terminated: np.ndarray   # bool[S, A, K]
+    start_thr: np.ndarray    # uint32[n_start]  thresholds of the start support (the last entry is 2**32 - 1)
+    start_state: np.ndarray  # int32[n_start]   the support, ascending
+    masks: np.ndarray | None  # bool[S, A] or None
+
+    @property
+    def state_size(self) -> int:
+        return int(self.thr.shape[0])
+
+    @property
+    def action_size(self) -> int:
+        return int(self.thr.shape[1])
+
+    @property
+    def k(self) -> int:
+        return int(self.thr.shape[2])
+
+
+def _thresholds(p: np.ndarray) -> np.ndarray:
+    """uint32 thresholds of probability lists along the last axis (zero-probability entries compacted away)."""
+    c = np.cumsum(p, axis=-1)
+    t = np.floor(c / c[..., -1:] * _TWO32)
+    return np.minimum(t, _TWO32 - 1.0).astype(np.uint32)
+
+
+def encode_table_mdp(probs, next_states, rewards, terminated, initial_state_distrib=None, action_masks=None) -> TableMDP:
+    """Encode a finite MDP for :class:`TabularMDPEnv` (and for any model that has to agree with it bit for bit).
+
+    ``probs``, ``next_states``, ``rewards``, ``terminated`` have shape ``[S, A, K]``: outcome ``k`` of ``(s, a)``; unused
+    slots have probability 0.  ``initial_state_distrib`` is a length-``S`` distribution (default: state 0), and
+    ``action_masks`` an optional ``bool[S, A]``.
+
+    Sampling is integer only.  The outcomes of ``(s, a)`` with a positive probability keep their order, outcomes of
+    probability 0 are dropped (they are never taken), and every outcome but the last gets the threshold
+    ``thr_k = min(floor(cumsum(p)[k] / cumsum(p)[-1] * 2**32), 2**32 - 1)`` computed in float64.  For a 32-bit word
+    ``u`` the outcome is the first ``k`` with ``u < thr_k``, else the last outcome.  In the result the last outcome and
+    the slots behind it (copies of it) carry ``2**32 - 1``, so that "the first slot with ``u < thr``, else the last
+    slot" is the same rule.  Rewards are rounded to float32.  The start distribution is encoded the same way over its
+    support (the states of positive probability, ascending).
+
+    Raises ``ValueError`` for bad shapes, probabilities that are negative or not finite, rewards that are not finite
+    after rounding to float32, an ``(s, a)`` (or a start
+    distribution) without positive probability or with more than ``MAX_OUTCOMES`` outcomes of positive probability,
+    and ``IndexError`` for states out of range.
+    """
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 3 or p.shape[0] < 1 or p.shape[1] < 1 or p.shape[2] < 1:
+        msg = f"probs must have shape [S, A, K], got {p.shape}"
+        raise ValueError(msg)
+    S, A, _ = p.shape
+    nxt = np.asarray(next_states)
+    rew64 = np.asarray(rewards, dtype=np.float64)
+    term = np.asarray(terminated)
+    for name, arr in (("next_states", nxt), ("rewards", rew64), ("terminated", term)):
+        if arr.shape != p.shape:
+            msg = f"{name} must have the shape of probs {p.shape}, got {arr.shape}"
+            raise ValueError(msg)
+    if not np.all(np.isfinite(p)) or np.any(p < 0):
+        msg = "outcome probabilities must be finite and >= 0"
+        raise ValueError(msg)
+    if not np.issubdtype(nxt.dtype, np.integer):
+        msg = f"next_states must be integers, got {nxt.dtype}"
+        raise ValueError(msg)
+    with np.errstate(over="ignore"):
+        rew = rew64.astype(np.float32)
+    if not np.all(np.isfinite(rew)):
+        msg = "rewards must be finite in float32 (the device env returns float32 rewards)"
+        raise ValueError(msg)
+    pos = p > 0
+    count = pos.sum(axis=-1)
+    if np.any(count == 0):
+        s, a = np.argwhere(count == 0)[0]
+        msg = f"(state {s}, action {a}) has no outcome of positive probability"
+        raise ValueError(msg)
+    k = int(count.max())
+    if k > MAX_OUTCOMES:
+        msg = f"at most {MAX_OUTCOMES} outcomes of positive probability per (state, action), got {k}"
+        raise ValueError(msg)
+    if np.any(nxt[pos] < 0) or np.any(nxt[pos] >= S):
+        msg = f"next state out of range [0, {S})"
+        raise IndexError(msg)
+    # compact the positive outcomes to the front (stable), then slot j reads outcome min(j, count - 1)
+    order = np.argsort(~pos, axis=-1, kind="stable")[..., :k]
+    take = lambda arr: np.take_along_axis(arr, order, axis=-1)  # noqa: E731
+    pc = take(p)
+    last = np.minimum(np.arange(k)[None, None, :], (count - 1)[..., None])
+    fill = lambda arr: np.take_along_axis(take(arr), last, axis=-1)  # noqa: E731
+    thr = _thresholds(pc)
+    thr[np.arange(k)[None, None, :] >= (count - 1)[..., None]] = np.uint32(0xFFFFFFFF)
+
+    if initial_state_distrib is None:
+        isd = np.zeros(S, dtype=np.float64)
+        isd[0] = 1.0
+    else:
+        isd = np.asarray(initial_state_distrib, dtype=np.float64)
+    if isd.shape != (S,):
+        msg = f"initial_state_distrib must have shape ({S},), got {isd.shape}"
+        raise ValueError(msg)
+    if not np.all(np.isfinite(isd)) or np.any(isd < 0) or not np.any(isd > 0):
+        msg = "initial_state_distrib must be finite, >= 0 and not all zero"
+        raise ValueError(msg)
+    support = np.flatnonzero(isd > 0)
+    start_thr = _thresholds(isd[support])
+    start_thr[-1] = np.uint32(0xFFFFFFFF)
+
+    masks = None
+    if action_masks is not None:
+        masks = np.asarray(action_masks)
+        if masks.shape != (S, A):
+            msg = f"action_masks must have shape ({S}, {A}), got {masks.shape}"
+            raise ValueError(msg)
+        masks = masks != 0
+    return TableMDP(thr, fill(nxt).astype(np.int32), fill(rew), fill(term != 0), start_thr,
+                    support.astype(np.int32), masks)
+
+
+def outcome_arrays(transitions, action_size=None):
+    """``transitions[s][a]`` = list of ``(prob, next_state, reward, terminated)`` (a dict keyed by state / action, as
+    gymnasium's toy-text ``P``, or nested sequences) -> ``(probs, next_states, rewards, terminated)`` of shape
+    ``[S, A, K]`` with ``K`` the longest list (shorter lists padded with probability 0)."""
+    keys = sorted(transitions) if isinstance(transitions, dict) else range(len(transitions))
+    if list(keys) != list(range(len(keys))):
+        msg = "transitions must list the states 0 .. S-1"
+        raise ValueError(msg)
+    S = len(keys)
+    rows = [transitions[s] for s in range(S)]
+    A = action_size
+    for s, row in enumerate(rows):
+        a_keys = sorted(row) if isinstance(row, dict) else range(len(row))
+        if list(a_keys) != list(range(len(a_keys))) or (A is not None and len(a_keys) != A):
+            msg = f"state {s}: the actions must be 0 .. A-1 with the same A for every state"
+            raise ValueError(msg)
+        A = len(a_keys)
+    if S == 0 or not A:
+        msg = "transitions must have at least one state and one action"
+        raise ValueError(msg)
+    K = max(len(rows[s][a]) for s in range(S) for a in range(A))
+    if K == 0:
+        msg = "every (state, action) needs at least one outcome"
+        raise ValueError(msg)
+    probs = np.zeros((S, A, K), dtype=np.float64)
+    nxt = np.zeros((S, A, K), dtype=np.int64)
+    rew = np.zeros((S, A, K), dtype=np.float64)  # (rounded to float32, and checked, by encode_table_mdp)
+    term = np.zeros((S, A, K), dtype=bool)
+    for s in range(S):
+        for a in range(A):
+            outs = rows[s][a]
+            if len(outs) == 0:
+                msg = f"(state {s}, action {a}) has no outcome"
+                raise ValueError(msg)
+            for j, out in enumerate(outs):
+                if len(out) != 4:
+                    msg = f"(state {s}, action {a}): outcomes are (prob, next_state, reward, terminated)"
+                    raise ValueError(msg)
+                p, n, r, t = out
+                if isinstance(n, (bool, np.bool_)) or not float(n).is_integer():
+                    msg = f"(state {s}, action {a}): next_state {n!r} is not an integer"
+                    raise ValueError(msg)
+                probs[s, a, j], nxt[s, a, j], rew[s, a, j], term[s, a, j] = p, int(n), r, t
+    return probs, nxt, rew, term
+
+
+class TabularMDPEnv(DeviceVecEnv):
+    """``num_agents`` copies of a finite MDP given as tables, stepped on the GPU (``qe_env_create_table``).
+
+    ``transitions[s][a]`` is a list of 1 .. 8 outcomes ``(prob, next_state, reward, terminated)`` (or an encoded
+    :class:`TableMDP`); ``initial_state_distrib`` a length-``S`` start distribution (default: state 0);
+    ``action_masks`` an optional ``bool[S, A]``, with which observations are ``{"observation", "action_mask"}``.
+    Outcomes and start states are drawn from a hash of (agent, seed, vector step) by the rule of
+    :func:`encode_table_mdp`; on termination the observation is already the next episode's first one (SAME_STEP
+    autoreset), and nothing is ever truncated.
+    """
+
+    kind = _lib.ENV_TABLE
+
+    def __init__(self, num_agents, transitions, initial_state_distrib=None, action_masks=None, seed=1, agent_offset=0):
+        if isinstance(transitions, TableMDP):
+            if initial_state_distrib is not None or action_masks is not None:
+                msg = "an encoded TableMDP already holds its start distribution and masks"
+                raise ValueError(msg)
+            mdp = transitions
+        else:
+            mdp = encode_table_mdp(*outcome_arrays(transitions), initial_state_distrib, action_masks)
+        p = _lib.EnvParams(kind=self.kind, masked=int(mdp.masks is not None), seed=int(seed) & 0xFFFFFFFF,
+                           agent_offset=int(agent_offset))
+        super().__init__(num_agents, mdp.state_size, mdp.action_size, p)
+        self.mdp = mdp
+        self.masked = mdp.masks is not None
+
+    @classmethod
+    def from_transition_dict(cls, P, num_agents, initial_state_distrib=None, action_masks=None, seed=1, agent_offset=0):
+        """From gymnasium's toy-text dynamics: ``P[s][a] = [(prob, next_state, reward, terminated), ...]`` (pass the
+        environment's ``initial_state_distrib`` along; gymnasium itself is not needed)."""
+        return cls(num_agents, P, initial_state_distrib, action_masks, seed=seed, agent_offset=agent_offset)
+
+    @classmethod
+    def from_arrays(cls, num_agents, next_states, rewards, terminated, initial_state_distrib=None, action_masks=None,
+                    seed=1, agent_offset=0):
+        """A deterministic MDP from dense ``[S, A]`` arrays of successors, rewards and termination flags."""
+        nxt = np.asarray(next_states)
+        if nxt.ndim != 2:
+            msg = f"next_states must have shape [S, A], got {nxt.shape}"
+            raise ValueError(msg)
+        rew = np.broadcast_to(np.asarray(rewards, dtype=np.float64), nxt.shape)
+        term = np.broadcast_to(np.asarray(terminated), nxt.shape)
+        mdp = encode_table_mdp(np.ones(nxt.shape + (1,)), nxt[..., None], rew[..., None], term[..., None],
+                               initial_state_distrib, action_masks)
+        return cls(num_agents, mdp, seed=seed, agent_offset=agent_offset)
+
+    def _create(self, algorithm) -> None:
+        m = self.mdp
+        # (C-contiguous copies that live through the call: the engine copies them to the device)
+        thr = np.ascontiguousarray(m.thr, dtype=np.uint32)
+        nxt = np.ascontiguousarray(m.next_state, dtype=np.int32)
+        rew = np.ascontiguousarray(m.reward, dtype=np.float32)
+        term = np.ascontiguousarray(m.terminated, dtype=np.uint8)
+        sthr = np.ascontiguousarray(m.start_thr, dtype=np.uint32)
+        sst = np.ascontiguousarray(m.start_state, dtype=np.int32)
+        masks = None if m.masks is None else np.ascontiguousarray(m.masks, dtype=np.uint8)
+        t = _lib.TableMdp(k=m.k, n_start=len(sst), thr=_lib.ptr(thr, C.c_uint32), next_state=_lib.ptr(nxt, C.c_int32),
+                          reward=_lib.ptr(rew, C.c_float), terminated=_lib.ptr(term, C.c_uint8),
+                          start_thr=_lib.ptr(sthr, C.c_uint32), start_state=_lib.ptr(sst, C.c_int32),
+                          masks=_lib.ptr(masks, C.c_uint8))
+        _lib.check(self._lib.qe_env_create_table(C.byref(self._h), algorithm.handle, self.num_agents,
+                                                 C.byref(self._params), C.byref(t)))

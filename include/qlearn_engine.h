@@ -57,7 +57,8 @@ enum qe_env_kind {
     QE_ENV_HASH = 0,  /* HashTabularEnv (build-defined synthetic MDP) */
     QE_ENV_GRID = 1,  /* GridLakeEnv: FrozenLake-style side x side grid */
     QE_ENV_BANDIT = 2, /* environments/rigged_two_armed_bandit.py:55-80 */
-    QE_ENV_TICTACTOE = 3 /* environments/tiktaktoe_mod.py:67-237 + flatten_multidiscrete_wrapper.py:106-161 */
+    QE_ENV_TICTACTOE = 3, /* environments/tiktaktoe_mod.py:67-237 + flatten_multidiscrete_wrapper.py:106-161 */
+    QE_ENV_TABLE = 4 /* a finite MDP given as tables (qe_env_create_table; not through qe_env_create) */
 };
 
 typedef struct qe_env_params {
@@ -180,6 +181,27 @@ int qe_learn(qe_engine* e, const int32_t* states, const int32_t* actions, const 
  * The batched env contract (environments/custom_env.py:31-84) as realised by
  * SyncVectorEnv(SAME_STEP) (benchmarks/throughput_benchmark.py:109-123). */
 int qe_env_create(qe_env** out, qe_engine* e, int64_t num_agents, const qe_env_params* p);
+/* A finite MDP given as tables (environments/device_envs.py:TabularMDPEnv encodes them).  Every (s, a) has `k` outcome
+ * slots (1 <= k <= 8), element [(s * A + a) * k + j] of the four outcome arrays; the outcome is the first j < k - 1 with
+ * u < thr[j], else slot k - 1 (unused slots repeat the last outcome), u a 32-bit word hashed from (agent_offset + agent,
+ * seed, vector step).  On termination the next observation is drawn from the start support the same way (first j <
+ * n_start - 1 with u' < start_thr[j], else the last entry; start_thr non-decreasing); the first reset draws from it too.
+ * masks: S * A bytes (non-zero = valid) or NULL; with masks the observations carry them, as a masked HASH env's do.
+ * All pointers are host pointers; the arrays are copied to the device and owned by the environment.  States out of
+ * range -> QE_ERR_INDEX; bad k / n_start / shapes -> QE_ERR_INVALID.  params->kind must be QE_ENV_TABLE (seed,
+ * agent_offset are used; masked is taken from `masks`). */
+typedef struct qe_table_mdp {
+    int32_t k;                  /* outcome slots per (state, action), 1..8 */
+    int32_t n_start;            /* entries of the start support, >= 1 */
+    const uint32_t* thr;        /* S*A*k */
+    const int32_t* next_state;  /* S*A*k */
+    const float* reward;        /* S*A*k */
+    const uint8_t* terminated;  /* S*A*k */
+    const uint32_t* start_thr;  /* n_start */
+    const int32_t* start_state; /* n_start */
+    const uint8_t* masks;       /* S*A or NULL */
+} qe_table_mdp;
+int qe_env_create_table(qe_env** out, qe_engine* e, int64_t num_agents, const qe_env_params* p, const qe_table_mdp* t);
 int qe_env_destroy(qe_env* env);
 int qe_env_reset(qe_env* env, int32_t has_seed, uint32_t seed);
 /* current observations (+ masks n*A bytes, + per-agent running episode returns); any may be NULL */
