@@ -4,6 +4,7 @@
 // environment; this file holds everything that is not templated on them.)
 #include "qe_host.h"
 #include "qe_delta_sort.h"
+#include "qe_rollout_df.h"
 
 namespace {
 thread_local std::string g_err;
@@ -106,29 +107,6 @@ static int slot_create(qe_engine* e, RolloutSlot& sl) {
     return QE_OK;
 }
 
-// Page-locked result block of a slot (persistent path), sized for `agents` agents.
-static int slot_host_block(qe_engine* e, RolloutSlot& sl, size_t agents) {
-    (void)e;
-    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
-    if (!sl.hb) {
-        HIP_TRY(hipHostMalloc((void**)&sl.hb, sizeof(HostBlock), flags));
-        memset(sl.hb, 0, sizeof(HostBlock));
-        HIP_TRY(hipHostMalloc((void**)&sl.hb_key, (size_t)HOST_LOG_CAP * sizeof(unsigned long long), flags));
-        HIP_TRY(hipHostMalloc((void**)&sl.hb_ret, (size_t)HOST_LOG_CAP * sizeof(float), flags));
-    }
-    if (agents > sl.hb_agents) {
-        for (void* h : {(void*)sl.hb_obs, (void*)sl.hb_aux, (void*)sl.hb_acc})
-            if (h) (void)hipHostFree(h);
-        sl.hb_obs = nullptr; sl.hb_aux = nullptr; sl.hb_acc = nullptr; sl.hb_agents = 0;
-        const size_t want = std::max(agents, (size_t)1024);
-        HIP_TRY(hipHostMalloc((void**)&sl.hb_obs, want * 4, flags));
-        HIP_TRY(hipHostMalloc((void**)&sl.hb_aux, want * 4, flags));
-        HIP_TRY(hipHostMalloc((void**)&sl.hb_acc, want * 4, flags));
-        sl.hb_agents = want;
-    }
-    return QE_OK;
-}
-
 // Room for a schedule plan of `count` steps (page-locked staging + device copy): sized generously and doubled
 // when outgrown, re-allocating pinned memory costs milliseconds.  No rollout may be in flight.
 static int plan_reserve(qe_engine* e, size_t count) {
@@ -195,10 +173,161 @@ void pack_masks(const uint8_t* masks, int64_t n, int A, std::vector<uint32_t>& o
             if (masks[i * A + j]) out[(size_t)i * nw + (j >> 5)] |= 1u << (j & 31);
 }
 
-// Enqueue one rollout (no host synchronisation): schedules, control block, kernels, events.
-template <typename T, class Env>
-int rollout_begin_impl(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps, int mode, int learn,
-                       int32_t* trace_host) {
+template <class F>
+int by_kind(int kind, F f) {
+    switch (kind) {
+        case QE_ENV_HASH: return f(HashEnv{});
+        case QE_ENV_GRID: return f(GridEnv{});
+        case QE_ENV_BANDIT: return f(BanditEnv{});
+        case QE_ENV_TICTACTOE: return f(TttEnv{});
+        case QE_ENV_TABLE: return f(TableEnv{});
+    }
+    return qe_fail(QE_ERR_INVALID, "unknown env kind %d", kind);
+}
+
+// f(T{}, Env{}) for the engine's table dtype and the environment: the instantiations of qe_inst_lane.hip / qe_inst_step.hip
+template <class F>
+int by_type(const qe_engine* e, const qe_env* env, F f) {
+    return by_kind(env->p.kind, [&](auto tag) { return e->dtype == QE_F32 ? f(float{}, tag) : f(double{}, tag); });
+}
+
+// ---- which kernels a rollout runs -----------------------------------------------------------------
+// The path of a call (QE_OPT_ROLLOUT_PATH: 0 automatic, 1 step-wise, 2 persistent, 3 wide, 4 turnstile):
+//   persistent -- one launch per rollout on one CU, one agent per lane (persistent_path);
+//   turnstile  -- one launch per step, all workgroups resident, rows handed from agent to agent (turn_fits), unless
+//                 its records found no room on this engine (turn_setup);
+//   wide       -- exact sequential updates for many agents, the ordered path spread over the chip in token rounds;
+//   step-wise  -- everything else; eval -- greedy evaluation.
+// A forced persistent path that does not fit comes out step-wise; rollout_begin rejects it.
+RolloutPath rollout_path(qe_engine* e, const qe_env* env, int learn) {
+    if (!learn) return RolloutPath::Eval;
+    if (persistent_path(e, env, learn)) return RolloutPath::Persistent;
+    const bool automatic = e->opt_path == 0 || e->opt_path == 4;
+    int& per_cu = e->turn_blocks_per_cu[env->p.kind];
+    if (automatic && per_cu == 0) {  // (asked once; without an answer the path is not taken)
+        per_cu = by_type(e, env, [&](auto t, auto tag) { return turn_occupancy<decltype(t), decltype(tag)>(e); });
+        if (per_cu <= 0) per_cu = -1;
+    }
+    if (automatic && turn_fits(e, env->N, per_cu) && !e->turn_no_memory) return RolloutPath::Turnstile;
+    if (e->opt_path == 3 || (automatic && env->N >= 2048)) return RolloutPath::Wide;
+    return RolloutPath::Stepwise;
+}
+
+// Persistent path: three builds for plain training rollouts of up to 128 agents (QE_OPT_LANE_ORDERED_PATH forces one):
+//   3 sparse   -- k_rollout_lane without the general ordered path (SEQ): steps with more than two touchers on a
+//                 row are worked off one agent per round; the fastest where rows are rarely shared (the shape
+//                 decides at first: agents^2 / states);
+//   1 dataflow -- k_rollout_df: the sharers of a row hand their values on in LDS; for shapes where most steps
+//                 have several of them;
+//   2 full     -- k_rollout_lane with slow_body: deep chains (dozens of agents on one state).
+// lane_build picks one for the next launch; learn_from_launch moves between them on what the previous launch counted.
+int lane_build(qe_engine* e, const qe_env* env) {
+    if (e->lane_light < 0) e->lane_light = (double)env->N * (double)env->N < 0.1 * (double)e->S ? 3 : 1;
+    int build = e->opt_lane_ordered ? e->opt_lane_ordered : e->lane_light;
+    // (the dataflow kernel's written-rows sets pack {row, owner} into 32 bits: state ids below 2^25)
+    if (build == 1 && e->S >= DF_MAX_STATES) build = 2;
+    if (build == 3 && env->N % 64 != 0) build = 1;  // (the sparse build exists for full wavefronts)
+    return build;
+}
+
+// The automatic choices of the next calls, from what this one counted: the persistent build and the token rounds of wide mode.
+void learn_from_launch(qe_engine* e, const RolloutSlot& sl, const Ctrl& fin) {
+    if (sl.steps <= 0) return;
+    if (sl.path == RolloutPath::Persistent) {
+        // The dataflow kernel unless its rounds ran long -- deep chains of row sharers, e.g. a hundred agents on one
+        // state, are what k_rollout_lane's ordered path (slow_body, run-ahead along same-cell chains) is for; that one
+        // reports the steps which needed it, and a launch of some length without any hands the next ones back to the
+        // dataflow kernel.
+        // (fin.pending_total: dataflow kernel = its rounds beyond the first of a step; k_rollout_lane = the steps in
+        // which a contested row had more than two touchers)
+        if (sl.variant & QE_VARIANT_DATAFLOW) {
+            if ((double)fin.pending_total > 16.0 * (double)sl.steps) e->lane_light = 2;  // deep chains: slow_body
+            // hardly anybody depended on anybody (fewer than one agent in two steps) on a shape whose rows are rarely
+            // shared: the sparse build's quiet step is the shorter one
+            else if (sl.steps >= 64 && (double)fin.involved_total < 0.5 * (double)sl.steps &&
+                     (double)sl.N * (double)sl.N < 0.1 * (double)e->S && sl.N % 64 == 0)
+                e->lane_light = 3;
+        } else if ((sl.variant >> 8) & 1) {  // the sparse build
+            if ((double)fin.pending_total > 0.01 * (double)sl.steps) e->lane_light = 1;  // rows are shared after all
+        } else if (fin.pending_total == 0 && sl.steps >= 64) {
+            e->lane_light = 1;
+        }
+    }
+    if (sl.path == RolloutPath::Wide) {
+        // every round roughly halves the agents that are left for the single-workgroup ordered path; aim at a few
+        // hundred of those per step
+        const double left = (double)fin.involved_total / (double)sl.steps;
+        if (left > 400.0) e->auto_rounds = std::min(MAX_TOKEN_ROUNDS, e->auto_rounds + 2);
+        else if (left < 100.0 && e->auto_rounds > 2) e->auto_rounds -= 1;
+    }
+}
+
+// ---- per-path setup of one rollout ----------------------------------------------------------------
+// Turnstile path: one 64-byte record per (row, step parity), 128 B per table row, allocated when the path is first
+// taken.  No room for them (a table that fills the device): e->turn_no_memory is set and the call runs the step-wise /
+// wide kernels instead, as for any shape the path does not take -- same results.
+int turn_setup(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps) {
+    const size_t recs = (size_t)e->S * 2;
+    const bool fresh = e->turn_rows.cap < recs;
+    if (fresh) {
+        const hipError_t err = e->turn_rows.ensure(recs);
+        if (err == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            e->turn_no_memory = true;
+            return QE_OK;
+        }
+        HIP_TRY(err);
+    }
+    HIP_TRY(env->turn_next.ensure((size_t)env->N * 4));
+    // the records carry a 32-bit step tag and are never cleared per step: zeroed when allocated and before a tag can repeat
+    if (fresh || ((e->turn_epoch + (unsigned long long)steps + 2ull) >> 31) != (e->turn_epoch >> 31))
+        HIP_TRY(hipMemsetAsync(e->turn_rows.p, 0, e->turn_rows.cap * sizeof(TurnRow), e->stream));
+    sl.turn_epoch = e->turn_epoch;
+    e->turn_epoch += (unsigned long long)steps + 2ull;  // tags of this call: epoch .. epoch + steps
+    return QE_OK;
+}
+
+// Wide mode: the token array (allocated on first use) and the rounds of this call.
+int wide_setup(qe_engine* e, RolloutSlot& sl) {
+    if (!e->tok) {
+        HIP_TRY(hipMalloc((void**)&e->tok, (size_t)e->S * 2 * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(e->tok, 0xFF, (size_t)e->S * 2 * sizeof(uint32_t), e->stream));
+    }
+    sl.rounds = e->opt_rounds ? e->opt_rounds : e->auto_rounds;
+    return QE_OK;
+}
+
+// Persistent path: the kernel publishes its results itself into page-locked, host-coherent memory (host result
+// block) sized for the environment's agents.  Both slots' blocks at once: a later, longer call that pipelines through
+// the other slot finds it ready.
+int host_block_setup(qe_engine* e, qe_env* env, RolloutSlot& sl) {
+    const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
+    for (RolloutSlot& each : e->slots) {
+        if (!each.hb) {
+            HIP_TRY(hipHostMalloc((void**)&each.hb, sizeof(HostBlock), flags));
+            memset(each.hb, 0, sizeof(HostBlock));
+            HIP_TRY(hipHostMalloc((void**)&each.hb_key, (size_t)HOST_LOG_CAP * sizeof(unsigned long long), flags));
+            HIP_TRY(hipHostMalloc((void**)&each.hb_ret, (size_t)HOST_LOG_CAP * sizeof(float), flags));
+        }
+        if ((size_t)env->N > each.hb_agents) {
+            for (void* h : {(void*)each.hb_obs, (void*)each.hb_aux, (void*)each.hb_acc})
+                if (h) (void)hipHostFree(h);
+            each.hb_obs = nullptr; each.hb_aux = nullptr; each.hb_acc = nullptr; each.hb_agents = 0;
+            const size_t want = std::max((size_t)env->N, (size_t)1024);
+            HIP_TRY(hipHostMalloc((void**)&each.hb_obs, want * 4, flags));
+            HIP_TRY(hipHostMalloc((void**)&each.hb_aux, want * 4, flags));
+            HIP_TRY(hipHostMalloc((void**)&each.hb_acc, want * 4, flags));
+            each.hb_agents = want;
+        }
+    }
+    sl.seq = ++e->seq_ctr;
+    return QE_OK;
+}
+
+// Kernel arguments of the rollout that `sl` has been set up for.
+template <typename T>
+Ctx<T> rollout_ctx(qe_engine* e, qe_env* env, const RolloutSlot& sl, int mode, const ReplayDev& rp) {
+    const bool learn = sl.path != RolloutPath::Eval;
     Ctx<T> c = env_ctx<T>(e, env);
     c.mode = mode;
     {   // Which family of selection variants the reference's dispatcher runs at this shape (q_learning_optimal.py:644-726,
@@ -217,106 +346,80 @@ int rollout_begin_impl(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps
     }
     if (sl.inline_sched) { c.thr = nullptr; c.lr = nullptr; }  // in the kernel-argument segment
     c.ep_key = sl.ep_key.p; c.ep_ret = sl.ep_ret.p; c.ep_cap = e->ep_cap;
-    const EnvCtx ev = make_envctx(e, env);
-    if (trace_host) {
-        HIP_TRY(e->trace.ensure((size_t)(steps * env->N)));
-        c.trace = e->trace.p;
-    }
+    if (sl.trace_host) c.trace = e->trace.p;
     if (e->dlog && learn) {
         c.dlog = e->dlog; c.dlog_base = e->dlog_count; c.dlog_cap = e->dlog_cap;
     }
+    c.rp = rp;
+    if (sl.path == RolloutPath::Turnstile) {
+        c.turn_next = env->turn_next.p; c.turn_rows = e->turn_rows.p; c.turn_epoch = sl.turn_epoch;
+    }
+    if (sl.path == RolloutPath::Wide) {
+        c.tok = e->tok; c.adv_bitmap = env->adv_bitmap.p;
+        // compacted lists pay for their two extra launches only when many rounds walk them
+        if (env->N >= e->listed_min && sl.rounds >= LISTED_MIN_ROUNDS) c.pend_list = env->pend_list.p;
+    }
+    if (sl.fast) {
+        c.hb = sl.hb; c.hb_obs = sl.hb_obs; c.hb_aux = sl.hb_aux; c.hb_acc = sl.hb_acc; c.hb_seq = sl.seq;
+        c.ep_key = sl.hb_key; c.ep_ret = sl.hb_ret; c.ep_cap = HOST_LOG_CAP;
+    }
+    return c;
+}
+
+// Enqueue one rollout on `path` (no host synchronisation): per-path setup, control block, kernels, events.
+int rollout_begin(qe_engine* e, qe_env* env, RolloutSlot& sl, RolloutPath path, int64_t steps, int mode,
+                  int32_t* trace_host) {
+    const bool learn = path != RolloutPath::Eval;
+    if (trace_host) HIP_TRY(e->trace.ensure((size_t)(steps * env->N)));
+    ReplayDev rp{};
     if (e->replay && learn) {  // device-to-device push of every transition (experience_replay.py:68-86)
         qe_replay* rb = e->replay;
-        c.rp = ReplayDev{rb->s.p, rb->a.p, rb->n.p, rb->r.p, rb->d.p, (long long)rb->capacity, (long long)rb->position};
+        rp = ReplayDev{rb->s.p, rb->a.p, rb->n.p, rb->r.p, rb->d.p, (long long)rb->capacity, (long long)rb->position};
         const int64_t pushed = steps * env->N;
         if (rb->position + pushed >= rb->capacity) rb->full = true;  // :85-86
         rb->position = (rb->position + pushed) % rb->capacity;
     }
-    const bool persistent = persistent_path(e, env, learn);
-    if (learn && e->opt_path == 2 && !persistent)
+    if (learn && e->opt_path == 2 && path != RolloutPath::Persistent)
         return qe_fail(QE_ERR_UNSUPPORTED, "persistent rollout needs num_agents <= 512 and action_size <= 64 (have %lld agents, %d actions)",
                     (long long)env->N, (int)e->A);
-    // turnstile path: one launch per step, all workgroups resident, rows handed from agent to agent
-    bool turn = false;
-    if (learn && !persistent && (e->opt_path == 4 || (e->opt_path == 0 && TURN_AUTO))) {
-        int& per_cu = e->turn_blocks_per_cu[env->p.kind];
-        if (per_cu == 0) {
-            per_cu = turn_occupancy<T, Env>(e);
-            if (per_cu <= 0) per_cu = -1;  // (asked once; without an answer the path is not taken)
-        }
-        turn = turn_fits(e, env->N, per_cu) && !e->turn_no_memory;
+    if (path == RolloutPath::Turnstile) {
+        if (int rc = turn_setup(e, env, sl, steps)) return rc;
+        if (e->turn_no_memory) path = rollout_path(e, env, learn);  // (now wide or step-wise)
     }
-    // one 64-byte record per (row, step parity): 128 B per table row, allocated when the path is first taken.  No room
-    // for them (a table that fills the device): the step-wise / wide kernels run instead, as for any shape the path
-    // does not take -- same results
-    const size_t recs = (size_t)e->S * 2;
-    const bool fresh = turn && e->turn_rows.cap < recs;
-    if (fresh) {
-        const hipError_t err = e->turn_rows.ensure(recs);
-        if (err == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            e->turn_no_memory = true;
-            turn = false;
-        } else {
-            HIP_TRY(err);
-        }
-    }
-    if (turn) {
-        HIP_TRY(env->turn_next.ensure((size_t)env->N * 4));
-        // the records carry a 32-bit step tag and are never cleared per step: zeroed when allocated and before a tag can repeat
-        if (fresh || ((e->turn_epoch + (unsigned long long)steps + 2ull) >> 31) != (e->turn_epoch >> 31))
-            HIP_TRY(hipMemsetAsync(e->turn_rows.p, 0, e->turn_rows.cap * sizeof(TurnRow), e->stream));
-        c.turn_next = env->turn_next.p; c.turn_rows = e->turn_rows.p;
-        c.turn_epoch = e->turn_epoch;
-        e->turn_epoch += (unsigned long long)steps + 2ull;  // tags of this call: epoch .. epoch + steps
-    }
-    // wide mode: exact sequential updates, many agents, ordered path spread over the chip
-    const bool wide = learn && !persistent && !turn &&
-                      (e->opt_path == 3 || ((e->opt_path == 0 || e->opt_path == 4) && env->N >= 2048));
-    if (wide) {
-        if (!e->tok) {
-            HIP_TRY(hipMalloc((void**)&e->tok, (size_t)e->S * 2 * sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(e->tok, 0xFF, (size_t)e->S * 2 * sizeof(uint32_t), e->stream));
-        }
-        c.tok = e->tok;
-        c.adv_bitmap = env->adv_bitmap.p;
-        sl.rounds = e->opt_rounds ? e->opt_rounds : e->auto_rounds;
-        // compacted lists pay for their two extra launches only when many rounds walk them
-        if (env->N >= e->listed_min && sl.rounds >= LISTED_MIN_ROUNDS) c.pend_list = env->pend_list.p;
-    }
-    sl.launches = 0; sl.n_samples = 0; sl.steps = steps; sl.N = env->N; sl.persistent = persistent;
-    sl.wide = wide; sl.turn = turn;
+    if (path == RolloutPath::Wide)
+        if (int rc = wide_setup(e, sl)) return rc;
+    const bool persistent = path == RolloutPath::Persistent;
+    sl.path = path;
+    sl.launches = 0; sl.n_samples = 0; sl.steps = steps; sl.N = env->N;
     sl.trace_host = trace_host;
-    sl.dbg = env->vinc.p;
     sl.env = env;
     env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
-    // The persistent kernel publishes its results itself (host result block).  With an action trace the
-    // trace still has to be copied out of device memory, which needs the end-of-kernel event anyway.
+    // With an action trace the trace still has to be copied out of device memory, which needs the end-of-kernel
+    // event anyway: no host result block then.
     sl.fast = persistent && e->opt_host_block && !trace_host;
-    if (sl.fast) {
-        // (both slots' blocks at once: a later, longer call that pipelines through the other slot finds it ready)
-        for (RolloutSlot& each : e->slots)
-            if (int rc = slot_host_block(e, each, (size_t)env->N)) return rc;
-        sl.seq = ++e->seq_ctr;
-        c.hb = sl.hb; c.hb_obs = sl.hb_obs; c.hb_aux = sl.hb_aux; c.hb_acc = sl.hb_acc; c.hb_seq = sl.seq;
-        c.ep_key = sl.hb_key; c.ep_ret = sl.hb_ret; c.ep_cap = HOST_LOG_CAP;
-    }
+    if (sl.fast)
+        if (int rc = host_block_setup(e, env, sl)) return rc;
     if (!persistent) HIP_TRY(hipMemsetAsync(sl.ctrl, 0, sizeof(Ctrl), e->stream));  // persistent kernel: in-kernel
     // Start marker of the timed region.  With the delta log attached a training call is chopped into
     // short launches (one per replica exchange) and every marker in the stream costs ~6 us between two
     // of them, so only every eighth launch is timed there; the others are reported at the last
     // measured time per step (and do not count as roofline samples).
-    sl.timed = !(persistent && c.dlog) || (e->timing_skip++ % 8) == 0;
+    sl.timed = !(persistent && e->dlog) || (e->timing_skip++ % 8) == 0;
     if (sl.fast && !e->opt_timing) sl.timed = false;  // in-kernel clock only
     if (sl.timed) HIP_TRY(hipEventRecord(sl.ev0, e->stream));
-    if (persistent) {
-        if (int rc = launch_persistent<T, Env>(e, env, sl, c, ev, steps, mode)) return rc;
-    } else if (learn) {
-        if (int rc = launch_stepwise<T, Env>(e, sl, c, ev, steps, turn)) return rc;
-        sl.variant = turn ? QE_VARIANT_TURNSTILE : (wide ? QE_VARIANT_WIDE : QE_VARIANT_STEPWISE);
-    } else {
-        if (int rc = launch_eval<T, Env>(e, sl, c, ev, steps)) return rc;
-    }
+    const int build = persistent ? lane_build(e, env) : 0;
+    const EnvCtx ev = make_envctx(e, env);
+    if (int rc = by_type(e, env, [&](auto t, auto tag) {
+            using T = decltype(t); using Env = decltype(tag);
+            const Ctx<T> c = rollout_ctx<T>(e, env, sl, mode, rp);
+            switch (path) {
+                case RolloutPath::Persistent: return launch_persistent<T, Env>(e, env, sl, c, ev, steps, mode, build);
+                case RolloutPath::Eval: return launch_eval<T, Env>(e, sl, c, ev, steps);
+                default: return launch_stepwise<T, Env>(e, sl, c, ev, steps, path == RolloutPath::Turnstile);
+            }
+        }))
+        return rc;
+    if (!persistent && learn) sl.variant = (int64_t)path;
     if (!persistent) {
         HIP_TRY(sl.ep_key_packed.ensure((size_t)e->ep_cap));
         HIP_TRY(sl.ep_ret_packed.ensure((size_t)e->ep_cap));
@@ -327,7 +430,7 @@ int rollout_begin_impl(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps
     }
     if (!sl.fast || sl.timed) HIP_TRY(hipEventRecord(sl.ev1, e->stream));
     HIP_TRY(hipGetLastError());
-    if (c.dlog) e->dlog_count = std::min<long long>(e->dlog_count + steps * env->N, e->dlog_cap);
+    if (e->dlog && learn) e->dlog_count = std::min<long long>(e->dlog_count + steps * env->N, e->dlog_cap);
     e->step_ctr += (uint64_t)steps;
     sl.busy = true;
     return QE_OK;
@@ -355,38 +458,39 @@ static int wait_host_block(qe_engine* e, RolloutSlot& sl) {
     return QE_OK;
 }
 
-// Wait for one enqueued rollout and read its results back on the copy stream (the compute stream
-// may already be running the next rollout).
-int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
-    if (!sl.busy) return qe_fail(QE_ERR_INVALID, "no rollout in flight in this slot");
-    sl.busy = false;
-    Ctrl fin{};
-    float ms = 0;
-    double clock_ms = 0.0;
-    if (sl.fast) {
-        if (int rc = wait_host_block(e, sl)) return rc;
-        fin.ep_count = sl.hb->ep_count; fin.involved_total = sl.hb->involved_total; fin.error = sl.hb->error;
-        fin.pending_total = sl.hb->complex_steps;
-        clock_ms = (double)(sl.hb->clk1 - sl.hb->clk0) / e->wall_clock_khz;
-        if (getenv("QE_PRINT_CLOCK") && sl.hb->clk1 > sl.hb->clk0)
-            fprintf(stderr, "  [clock] %.0f MHz shader clock over %.1f us (%lld steps)\n",
-                    (double)(sl.hb->cyc1 - sl.hb->cyc0) / ((double)(sl.hb->clk1 - sl.hb->clk0) / e->wall_clock_khz * 1e3),
-                    clock_ms * 1e3, (long long)sl.steps);
-        if (sl.timed) HIP_TRY(hipEventSynchronize(sl.ev1));
-        if (e->replay) HIP_TRY(hipStreamSynchronize(e->stream));  // ring entries are read through other streams
-        // the environment's state after this rollout sits in the block (unless the next rollout of a
-        // pipelined call is already moving it on)
-        const RolloutSlot& other = e->slots[&sl == &e->slots[0] ? 1 : 0];
-        if (sl.env && !(other.busy && other.env == sl.env)) {
-            sl.env->mirror_obs = sl.hb_obs; sl.env->mirror_aux = sl.hb_aux; sl.env->mirror_acc = sl.hb_acc;
-        }
-    } else {
+
+// Control words of a finished rollout: from the host result block, or copied out of device memory on the copy stream
+// (the compute stream may already be running the next rollout).  clock_ms: the kernel's own clock (host block only).
+int read_control(qe_engine* e, RolloutSlot& sl, Ctrl& fin, double& clock_ms) {
+    if (!sl.fast) {
         HIP_TRY(hipStreamWaitEvent(e->copy_stream, sl.ev1, 0));
         HIP_TRY(hipMemcpyAsync(sl.h_ctrl.p, sl.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->copy_stream));
         HIP_TRY(hipStreamSynchronize(e->copy_stream));
         HIP_TRY(hipGetLastError());
         fin = *sl.h_ctrl.p;
+        return QE_OK;
     }
+    if (int rc = wait_host_block(e, sl)) return rc;
+    fin.ep_count = sl.hb->ep_count; fin.involved_total = sl.hb->involved_total; fin.error = sl.hb->error;
+    fin.pending_total = sl.hb->complex_steps;
+    clock_ms = (double)(sl.hb->clk1 - sl.hb->clk0) / e->wall_clock_khz;
+    if (getenv("QE_PRINT_CLOCK") && sl.hb->clk1 > sl.hb->clk0)
+        fprintf(stderr, "  [clock] %.0f MHz shader clock over %.1f us (%lld steps)\n",
+                (double)(sl.hb->cyc1 - sl.hb->cyc0) / ((double)(sl.hb->clk1 - sl.hb->clk0) / e->wall_clock_khz * 1e3),
+                clock_ms * 1e3, (long long)sl.steps);
+    if (sl.timed) HIP_TRY(hipEventSynchronize(sl.ev1));
+    if (e->replay) HIP_TRY(hipStreamSynchronize(e->stream));  // ring entries are read through other streams
+    // the environment's state after this rollout sits in the block (unless the next rollout of a
+    // pipelined call is already moving it on)
+    const RolloutSlot& other = e->slots[&sl == &e->slots[0] ? 1 : 0];
+    if (sl.env && !(other.busy && other.env == sl.env)) {
+        sl.env->mirror_obs = sl.hb_obs; sl.env->mirror_aux = sl.hb_aux; sl.env->mirror_acc = sl.hb_acc;
+    }
+    return QE_OK;
+}
+
+// Device time of a finished rollout: its event pair, else the kernel's own clock, else the last measured time per step.
+int call_time(qe_engine* e, const RolloutSlot& sl, double clock_ms, float& ms) {
     if (sl.timed) {
         HIP_TRY(hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
         if (sl.steps > 0) e->ms_per_step_est = (double)ms / (double)sl.steps;
@@ -396,48 +500,22 @@ int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
     } else {
         ms = (float)(e->ms_per_step_est * (double)sl.steps);
     }
-    if (sl.persistent && sl.steps > 0) {
-        // Which build of the persistent kernel the NEXT launches of up to 128 agents take: the dataflow kernel
-        // (qe_rollout_df.h; it reports its dataflow rounds beyond the first of a step) unless those ran long -- deep
-        // chains of row sharers, e.g. a hundred agents on one state, are what k_rollout_lane's ordered path
-        // (slow_body, run-ahead along same-cell chains) is for; that one reports the steps which needed it, and a
-        // launch of some length without any hands the next ones back to the dataflow kernel.
-        // (fin.pending_total: dataflow kernel = its rounds beyond the first of a step; k_rollout_lane = the steps in
-        // which a contested row had more than two touchers)
-        if (sl.variant & QE_VARIANT_DATAFLOW) {
-            if ((double)fin.pending_total > 16.0 * (double)sl.steps) e->lane_light = 2;  // deep chains: slow_body
-            // hardly anybody depended on anybody (fewer than one agent in two steps) on a shape whose rows are rarely
-            // shared: the sparse build's quiet step is the shorter one
-            else if (sl.steps >= 64 && (double)fin.involved_total < 0.5 * (double)sl.steps &&
-                     (double)sl.N * (double)sl.N < 0.1 * (double)e->S && sl.N % 64 == 0)
-                e->lane_light = 3;
-        } else if ((sl.variant >> 8) & 1) {  // the sparse build
-            if ((double)fin.pending_total > 0.01 * (double)sl.steps) e->lane_light = 1;  // rows are shared after all
-        } else if (fin.pending_total == 0 && sl.steps >= 64) {
-            e->lane_light = 1;
-        }
-    }
-    if (sl.wide && sl.steps > 0) {
-        // Number of chip-wide token rounds of the NEXT calls: every round roughly halves the agents that
-        // are left for the single-workgroup ordered path; aim at a few hundred of those per step.
-        const double left = (double)fin.involved_total / (double)sl.steps;
-        if (left > 400.0) e->auto_rounds = std::min(MAX_TOKEN_ROUNDS, e->auto_rounds + 2);
-        else if (left < 100.0 && e->auto_rounds > 2) e->auto_rounds -= 1;
-    }
-    // episode log -> host, sorted by (step, agent) = append order of base_runtime.py:218-221.
-    // The persistent kernel writes a linear log (ep_count entries); the step-wise kernels write 64
-    // segments of ep_cap/64 entries each (ep_seg[] counts).
+    return QE_OK;
+}
+
+// Episode log -> e->ep_host, sorted by (step, agent) = append order of base_runtime.py:218-221.
+// The persistent kernel writes a linear log (ep_count entries); the step-wise kernels write 64
+// segments of ep_cap/64 entries each (ep_seg[] counts).  total: episodes finished, got: entries kept.
+int fetch_episode_log(qe_engine* e, RolloutSlot& sl, const Ctrl& fin, long long& total, long long& got) {
+    const bool persistent = sl.path == RolloutPath::Persistent;
     const long long seg_cap = e->ep_cap >> 6;
-    long long total = 0, got = 0;
-    long long seg_got[64];
-    if (sl.persistent) {
+    if (persistent) {
         total = (long long)fin.ep_count;
         got = std::min<long long>(total, sl.fast ? HOST_LOG_CAP : e->ep_cap);
     } else {
         for (int k = 0; k < 64; ++k) {
             total += fin.ep_seg[k];
-            seg_got[k] = std::min<long long>(fin.ep_seg[k], seg_cap);
-            got += seg_got[k];
+            got += std::min<long long>(fin.ep_seg[k], seg_cap);
         }
     }
     e->ep_host.resize((size_t)got);
@@ -458,45 +536,47 @@ int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
                 if (int rc = warm_pinned(e, each.h_ret.p, each.h_ret.cap * 4)) return rc;
             }
         }
-        if (sl.persistent) {
-            HIP_TRY(hipMemcpyAsync(sl.h_key.p, sl.ep_key.p, got * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->copy_stream));
-            HIP_TRY(hipMemcpyAsync(sl.h_ret.p, sl.ep_ret.p, got * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
-        } else {  // packed by k_log_gather at the end of the rollout
-            HIP_TRY(hipMemcpyAsync(sl.h_key.p, sl.ep_key_packed.p, got * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->copy_stream));
-            HIP_TRY(hipMemcpyAsync(sl.h_ret.p, sl.ep_ret_packed.p, got * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
-        }
+        // (step-wise kernels: packed by k_log_gather at the end of the rollout)
+        const unsigned long long* key = persistent ? sl.ep_key.p : sl.ep_key_packed.p;
+        const float* ret = persistent ? sl.ep_ret.p : sl.ep_ret_packed.p;
+        HIP_TRY(hipMemcpyAsync(sl.h_key.p, key, got * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->copy_stream));
+        HIP_TRY(hipMemcpyAsync(sl.h_ret.p, ret, got * sizeof(float), hipMemcpyDeviceToHost, e->copy_stream));
         HIP_TRY(hipStreamSynchronize(e->copy_stream));
         for (long long k = 0; k < got; ++k) e->ep_host[(size_t)k] = {sl.h_key.p[k], sl.h_ret.p[k]};
     }
     sort_episode_log(e->ep_host, e->ep_tmp);
-    if (sl.trace_host) {
-        HIP_TRY(hipMemcpyAsync(sl.trace_host, e->trace.p, sl.steps * sl.N * sizeof(int32_t), hipMemcpyDeviceToHost, e->copy_stream));
-        HIP_TRY(hipStreamSynchronize(e->copy_stream));
+    return QE_OK;
+}
+
+void fill_stats(const RolloutSlot& sl, const Ctrl& fin, float ms, double clock_ms, long long total, long long got,
+                qe_rollout_stats* st) {
+    const bool persistent = sl.path == RolloutPath::Persistent;
+    memset(st, 0, sizeof *st);
+    st->kernel_ms = ms; st->launches = sl.launches; st->episodes = (int64_t)total;
+    st->involved = (int64_t)fin.involved_total;
+    st->episodes_dropped = (int64_t)(total - got);
+    for (int k = 0; k < sl.n_samples; ++k) {
+        float one = 0;
+        if (hipEventElapsedTime(&one, sl.sample_ev[2 * k], sl.sample_ev[2 * k + 1]) == hipSuccess)
+            st->dominant_ms += one;
     }
-    if (st) {
-        memset(st, 0, sizeof *st);
-        st->kernel_ms = ms; st->launches = sl.launches; st->episodes = (int64_t)total;
-        st->involved = (int64_t)fin.involved_total;
-        st->episodes_dropped = (int64_t)(total - got);
-        for (int k = 0; k < sl.n_samples; ++k) {
-            float one = 0;
-            if (hipEventElapsedTime(&one, sl.sample_ev[2 * k], sl.sample_ev[2 * k + 1]) == hipSuccess)
-                st->dominant_ms += one;
-        }
-        st->dominant_launches = sl.n_samples;
-        st->dominant_env_steps = (int64_t)sl.n_samples * sl.N;
-        if (sl.persistent && sl.timed) {  // the one launch IS the timed region
-            st->dominant_ms = ms; st->dominant_launches = 1; st->dominant_env_steps = sl.steps * sl.N;
-        }
-        st->device_clock_ms = clock_ms;
-        st->kernel_variant = sl.variant;
-        st->complex_steps = sl.persistent ? (int64_t)fin.pending_total : 0;
+    st->dominant_launches = sl.n_samples;
+    st->dominant_env_steps = (int64_t)sl.n_samples * sl.N;
+    if (persistent && sl.timed) {  // the one launch IS the timed region
+        st->dominant_ms = ms; st->dominant_launches = 1; st->dominant_env_steps = sl.steps * sl.N;
     }
+    st->device_clock_ms = clock_ms;
+    st->kernel_variant = sl.variant;
+    st->complex_steps = persistent ? (int64_t)fin.pending_total : 0;
+}
+
+// Printers of the diagnostic builds (-DQE_TURN_CLOCKS, -DQE_STAMPS): what the kernels left in the environment's vinc.
+void print_diagnostics(const RolloutSlot& sl) {
 #ifdef QE_TURN_CLOCKS
-    if (sl.turn && getenv("QE_PRINT_TURN_CLOCKS")) {
+    if (sl.path == RolloutPath::Turnstile && getenv("QE_PRINT_TURN_CLOCKS")) {
         static unsigned long long raw[512 * 8 * 8], clk[512 * 8];
-        (void)hipMemcpy(raw, sl.dbg, sizeof raw, hipMemcpyDeviceToHost);
-        (void)hipMemset(sl.dbg, 0, sizeof raw);
+        (void)hipMemcpy(raw, sl.env->vinc.p, sizeof raw, hipMemcpyDeviceToHost);
+        (void)hipMemset(sl.env->vinc.p, 0, sizeof raw);
         for (int k = 0; k < 512 * 8; ++k) { clk[k] = 0; for (int w = 0; w < 8; ++w) clk[k] = std::max(clk[k], raw[8 * k + w]); }
         const char* names[8] = {"", "contested: classified", "last update starts", "last update issued", "last contested agent done",
                                 "last plain agent done", "first loads back", ""};
@@ -515,7 +595,7 @@ int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
 #ifdef QE_STAMPS
     if (getenv("QE_PRINT_STAMPS")) {
         double seg[24];
-        (void)hipMemcpy(seg, sl.dbg, sizeof seg, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(seg, sl.env->vinc.p, sizeof seg, hipMemcpyDeviceToHost);
         const char* names[8] = {"inserts", "barrier", "row issue+classify", "philox", "update+account",
                                 "select+env", "extended+flush", "loop top"};
         for (int k = 0; k < 8; ++k) fprintf(stderr, "  [stamps] %-20s %8.1f ns/step\n", names[k], seg[k] * 10.0 / sl.steps);
@@ -526,34 +606,29 @@ int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
                 seg[16], seg[17], seg[18], seg[19] * 10.0 / sl.steps);
     }
 #endif
+}
+
+// Wait for one enqueued rollout and read its results back.
+int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
+    if (!sl.busy) return qe_fail(QE_ERR_INVALID, "no rollout in flight in this slot");
+    sl.busy = false;
+    Ctrl fin{};
+    double clock_ms = 0.0;
+    float ms = 0;
+    long long total = 0, got = 0;
+    if (int rc = read_control(e, sl, fin, clock_ms)) return rc;
+    if (int rc = call_time(e, sl, clock_ms, ms)) return rc;
+    learn_from_launch(e, sl, fin);
+    if (int rc = fetch_episode_log(e, sl, fin, total, got)) return rc;
+    if (sl.trace_host) {
+        HIP_TRY(hipMemcpyAsync(sl.trace_host, e->trace.p, sl.steps * sl.N * sizeof(int32_t), hipMemcpyDeviceToHost, e->copy_stream));
+        HIP_TRY(hipStreamSynchronize(e->copy_stream));
+    }
+    if (st) fill_stats(sl, fin, ms, clock_ms, total, got, st);
+    print_diagnostics(sl);
     if (fin.error == ERR_EMPTY_CHOICE) return qe_fail(QE_ERR_INDEX, "Cannot choose from an empty sequence");
     if (fin.error) return qe_fail(QE_ERR_NO_DEVICE, "ordered path gave up (internal error %u)", fin.error);
     return QE_OK;
-}
-
-template <typename T>
-int rollout_begin_dispatch(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps, int mode, int learn,
-                           int32_t* trace) {
-    switch (env->p.kind) {
-        case QE_ENV_HASH: return rollout_begin_impl<T, HashEnv>(e, env, sl, steps, mode, learn, trace);
-        case QE_ENV_GRID: return rollout_begin_impl<T, GridEnv>(e, env, sl, steps, mode, learn, trace);
-        case QE_ENV_BANDIT: return rollout_begin_impl<T, BanditEnv>(e, env, sl, steps, mode, learn, trace);
-        case QE_ENV_TICTACTOE: return rollout_begin_impl<T, TttEnv>(e, env, sl, steps, mode, learn, trace);
-        case QE_ENV_TABLE: return rollout_begin_impl<T, TableEnv>(e, env, sl, steps, mode, learn, trace);
-    }
-    return qe_fail(QE_ERR_INVALID, "unknown env kind %d", env->p.kind);
-}
-
-template <class F>
-int by_kind(int kind, F f) {
-    switch (kind) {
-        case QE_ENV_HASH: return f(HashEnv{});
-        case QE_ENV_GRID: return f(GridEnv{});
-        case QE_ENV_BANDIT: return f(BanditEnv{});
-        case QE_ENV_TICTACTOE: return f(TttEnv{});
-        case QE_ENV_TABLE: return f(TableEnv{});
-    }
-    return qe_fail(QE_ERR_INVALID, "unknown env kind %d", kind);
 }
 
 int check_indices(const int32_t* v, int64_t n, int64_t bound, const char* what) {
@@ -611,8 +686,6 @@ int qe_create(qe_engine** out, int64_t S, int32_t A, double gamma, uint64_t seed
     if (err == hipSuccess) err = hipMalloc(&e->q, bytes);
     if (err == hipSuccess) err = hipMalloc((void**)&e->stamps, (size_t)S * 2 * sizeof(unsigned long long));
     if (err == hipSuccess) err = hipMalloc((void**)&e->ctrl, sizeof(Ctrl));
-    if (err == hipSuccess) err = hipEventCreate(&e->ev0);
-    if (err == hipSuccess) err = hipEventCreate(&e->ev1);
     if (err == hipSuccess) err = hipMemsetAsync(e->q, 0, bytes, e->stream);
     if (err == hipSuccess && e->ld > e->A) {  // padding columns hold -inf (see load_row_lane)
         const int64_t cells = S * (int64_t)(e->ld - e->A);
@@ -661,8 +734,6 @@ int qe_destroy(qe_engine* e) {
     if (e->ctrl) (void)hipFree(e->ctrl);
     if (e->tok) (void)hipFree(e->tok);
     e->turn_rows.release();
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
     e->slots[0].release(); e->slots[1].release();
     if (e->plan_ready) (void)hipEventDestroy(e->plan_ready);
     e->plan_thr.release(); e->plan_lr.release(); e->h_plan_thr.release(); e->h_plan_lr.release();
@@ -1210,10 +1281,10 @@ static int begin(qe_engine* e, qe_env* env, int64_t steps, const double* eps, co
     RolloutSlot& sl = e->slots[slot];
     if (sl.busy) return qe_fail(QE_ERR_INVALID, "slot %d still has a rollout in flight (call qe_rollout_end)", slot);
     HIP_TRY(hipSetDevice(e->device));
+    const RolloutPath path = rollout_path(e, env, learn);
     if (int rc = slot_prepare(e, sl, steps, learn ? eps : nullptr, learn ? lr : nullptr, use_plan,
-                              persistent_path(e, env, learn) && !trace)) return rc;
-    return e->dtype == QE_F32 ? rollout_begin_dispatch<float>(e, env, sl, steps, mode, learn, trace)
-                              : rollout_begin_dispatch<double>(e, env, sl, steps, mode, learn, trace);
+                              path == RolloutPath::Persistent && !trace)) return rc;
+    return rollout_begin(e, env, sl, path, steps, mode, trace);
 }
 
 static double now_us() {
@@ -1253,9 +1324,9 @@ int qe_schedule_plan(qe_engine* e, const double* eps, const double* lr, int64_t 
 
 int64_t qe_rollout_chunk_limit(qe_engine* e, qe_env* env, int32_t learn) {
     if (!e || !env) return 0;
-    // worst case: every agent finishes an episode in every step
-    if (persistent_path(e, env, learn) && e->opt_host_block) return std::max<int64_t>(1, HOST_LOG_CAP / env->N);
-    if (persistent_path(e, env, learn)) return std::max<int64_t>(1, e->ep_cap / env->N);
+    // worst case: every agent finishes an episode in every step.  The persistent kernel writes one linear log (the
+    // path rollout_path takes first; asked without the turnstile's occupancy query, which the answer does not need)
+    if (persistent_path(e, env, learn)) return std::max<int64_t>(1, (e->opt_host_block ? HOST_LOG_CAP : e->ep_cap) / env->N);
     // step-wise / evaluation kernels: 64 log segments chosen by (agent + step) & 63, each ep_cap / 64 entries
     const int64_t per_seg_step = (env->N + 63) / 64;
     return std::max<int64_t>(1, (e->ep_cap >> 6) / per_seg_step);

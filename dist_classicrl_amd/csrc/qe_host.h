@@ -1,7 +1,8 @@
 // qe_host.h -- host-side state of libqlearn_engine.so shared by its translation units: the engine / environment /
 // rollout-slot structures, small helpers, and the launch entry points whose kernel instantiations are compiled
 // in separate files (qe_inst_lane.hip: persistent path, qe_inst_step.hip: step-wise / wide / turnstile paths and
-// evaluation), one object per (table dtype, environment), so that the library builds in parallel.
+// evaluation), one object per (table dtype, environment), so that the library builds in parallel.  Which of them a
+// rollout runs is decided in qe_engine.hip (rollout_path; lane_build for the persistent builds).
 #pragma once
 #include "../../include/qlearn_engine.h"
 
@@ -84,6 +85,10 @@ constexpr int LISTED_RECOMPACT = 3;    // rounds on the first list before the se
 constexpr unsigned LISTED_GRID = 1024; // blocks of a listed round (grid-stride)
 constexpr long long HOST_LOG_CAP = 1 << 18;  // episode-log entries of a slot's host result block (persistent path)
 
+// The kernels a rollout runs, chosen once per call by rollout_path (qe_engine.hip).  The values are the path bits of
+// qe_rollout_stats::kernel_variant (QE_VARIANT_* below).
+enum class RolloutPath : int { Stepwise = 1, Persistent = 2, Wide = 3, Turnstile = 4, Eval = 5 };
+
 // Everything one in-flight rollout owns, so that the next rollout can be enqueued before the results
 // of the previous one are read back.
 struct RolloutSlot {
@@ -97,15 +102,16 @@ struct RolloutSlot {
     PinnedBuf<Ctrl> h_ctrl;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, sched_ready = nullptr;
     std::vector<hipEvent_t> sample_ev;  // event pairs around sampled dominant-kernel launches
-    bool busy = false, persistent = false, wide = false, turn = false, timed = true;
+    bool busy = false, timed = true;
+    RolloutPath path = RolloutPath::Stepwise;  // of the rollout in flight
     int n_samples = 0;
     int64_t steps = 0, N = 0, launches = 0;
     int64_t variant = 0;  // qe_rollout_stats::kernel_variant of the rollout in flight
     int32_t* trace_host = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int rounds = 4;  // token rounds per step of this call (wide mode)
+    unsigned long long turn_epoch = 0;  // turnstile path: record tag of this call's step 0
     int64_t plan_offset = -1;  // >= 0: schedules come from the engine's plan at this offset
-    double* dbg = nullptr;  // env->vinc of the rollout in flight (diagnostic builds)
     // Host result block (persistent path): page-locked, host-coherent memory the rollout kernel writes
     // itself -- control words, final observations / env state / running returns, episode log -- so that
     // qe_rollout_end neither synchronises a stream nor issues a copy: it spins on hb->seq.
@@ -171,7 +177,7 @@ struct qe_engine {
     int opt_stamp_bits = 0;    // QE_OPT_STAMP_HASH_BITS: 0 = automatic, else log2 of the hashed touch-counter slots
     int opt_turn_poll = 0;     // QE_OPT_TURN_POLL: 1 = progress words are polled with sc1 loads, 0 (default) = with returning atomics
     int opt_lane_ordered = 0;  // QE_OPT_LANE_ORDERED_PATH: 0 = automatic, 1 = dataflow kernel, 2 = full build, 3 = sparse build
-    int lane_light = -1;       // automatic choice for the next launch (same values; -1: not decided yet)
+    int lane_light = -1;       // automatic choice for the next launch (same values; -1: not decided yet; lane_build)
     unsigned long long seq_ctr = 0;
     double host_begin_us = 0.0;  // diagnostics (QE_PRINT_HOST)
     hipStream_t stream = nullptr;
@@ -180,7 +186,6 @@ struct qe_engine {
     unsigned long long* stamps = nullptr;
     Ctrl* ctrl = nullptr;
     uint32_t* tok = nullptr;  // [2][S] wide-mode tokens, allocated on first use, all TOK_INF at rest
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // schedules
     DevBuf<unsigned long long> thr;
     DevBuf<double> lr;
@@ -318,13 +323,12 @@ inline unsigned grid_for(int64_t threads, int block) { return (unsigned)((thread
 // chip is left out of the count, for kernels that share it with the rollout (the collectives of the replica exchange
 // run beside the next chunk).  The progress counts are 16 bits.
 constexpr int TURN_RESERVE_DIV = 4;   // 1 / TURN_RESERVE_DIV of the CUs is not counted on
-constexpr bool TURN_AUTO = true;  // automatic choice for agent counts above the persistent kernel's
 inline bool turn_fits(const qe_engine* e, int64_t N, int blocks_per_cu) {
     const int64_t blocks = (N * e->L + TURN_BLOCK - 1) / TURN_BLOCK;
     const int64_t cus = (int64_t)e->num_cus - e->num_cus / TURN_RESERVE_DIV;
     return N <= 60000 && blocks_per_cu > 0 && blocks <= cus * blocks_per_cu && e->ld <= 256;
 }
-// one launch per rollout on one CU, one agent per lane with its whole row in registers (qe_rollout_lane.h)
+// one launch per rollout on one CU, one agent per lane with its whole row in registers (qe_rollout_lane.h; rollout_path)
 inline bool persistent_path(const qe_engine* e, const qe_env* env, int learn) {
     return learn && env->N <= LANE_MAX_AGENTS && e->ld <= 64 && (e->opt_path == 0 || e->opt_path == 2);
 }
@@ -342,10 +346,13 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   512-agent build, bit 10 the dataflow kernel (k_rollout_df), bits 12-19 NV (16-byte loads per fp32 row), bit 20
 //   masked environment
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
-constexpr int64_t QE_VARIANT_STEPWISE = 1, QE_VARIANT_PERSISTENT = 2, QE_VARIANT_WIDE = 3, QE_VARIANT_TURNSTILE = 4,
-                  QE_VARIANT_EVAL = 5;
+constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
+                  QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
+                  QE_VARIANT_EVAL = (int64_t)RolloutPath::Eval;
+// build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
-int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode);
+int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
+                      int build);
 template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>

@@ -15,7 +15,8 @@ constexpr int64_t lane_variant() {
 }
 
 template <typename T, class Env>
-int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode) {
+int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
+                      int build) {
     const unsigned block = (unsigned)((env->N + 63) / 64 * 64);
     int flags = FLAG_ACCOUNT;
 #ifdef QE_EXPERIMENT
@@ -31,20 +32,8 @@ int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& 
                                   ((std::is_same<Env, HashEnv>::value && !MK && (NV == 2 || NV == 4)) ||
                                    std::is_same<Env, TttEnv>::value);
         const bool full = (int64_t)block == env->N;  // every lane of the agents' wavefronts holds an agent
-        // Three builds for plain training rollouts of up to 128 agents (QE_OPT_LANE_ORDERED_PATH forces one):
-        //   3 sparse  -- k_rollout_lane without the general ordered path (SEQ): steps with more than two touchers on a
-        //                row are worked off one agent per round; the fastest where rows are rarely shared (the shape
-        //                decides at first: agents^2 / states);
-        //   1 dataflow -- k_rollout_df: the sharers of a row hand their values on in LDS; for shapes where most steps
-        //                have several of them;
-        //   2 full    -- k_rollout_lane with slow_body: deep chains (dozens of agents on one state).
-        // rollout_end moves between them on what the previous launch counted.
-        if (e->lane_light < 0) e->lane_light = (double)env->N * (double)env->N < 0.1 * (double)e->S ? 3 : 1;
-        int choice = e->opt_lane_ordered ? e->opt_lane_ordered : e->lane_light;
-        // (the dataflow kernel's written-rows sets pack {row, owner} into 32 bits: state ids below 2^25)
-        if (choice == 1 && e->S >= DF_MAX_STATES) choice = 2;
-        if (choice == 3 && !full) choice = 1;  // (the sparse build exists for full wavefronts)
-        const bool light = choice == 1, sparse = choice == 3;
+        // the three builds for plain training rollouts of up to 128 agents (see lane_build)
+        const bool light = build == 1, sparse = build == 3;
         auto launch = [&](auto cap, auto lean_c, auto help, auto full_c, auto seq, unsigned threads) {
             constexpr int CAP = decltype(cap)::value, LEAN = decltype(lean_c)::value;
             constexpr bool HELP = decltype(help)::value, FULL = decltype(full_c)::value, SEQ = decltype(seq)::value;
@@ -70,18 +59,17 @@ int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& 
         using L2 = std::integral_constant<int, HAS_LEAN ? 2 : 0>;
         using Y = std::integral_constant<bool, HAS_LEAN>;
         using N = std::false_type;
+        auto by_lean = [&](auto f) { if (c.dlog) f(L2{}); else f(L1{}); };  // L2: + delta log of the replica exchange
         // (light: no wavefronts beyond the agents' and the draw producers' -- the others only serve the general ordered path)
-        if (HAS_LEAN && lean && block <= 128 && !c.dlog && full && sparse) launch(I128{}, L1{}, Y{}, Y{}, Y{}, 2 * block);
-        else if (HAS_LEAN && lean && block <= 128 && full && sparse) launch(I128{}, L2{}, Y{}, Y{}, Y{}, 2 * block);
-        else if (HAS_LEAN && lean && block <= 128 && !c.dlog && full && light) launch_df(L1{}, Y{});
-        else if (HAS_LEAN && lean && block <= 128 && full && light) launch_df(L2{}, Y{});  // + delta log of the replica exchange
-        else if (HAS_LEAN && lean && block <= 128 && !c.dlog && light) launch_df(L1{}, N{});
-        else if (HAS_LEAN && lean && block <= 128 && light) launch_df(L2{}, N{});
-        else if (HAS_LEAN && lean && block <= 128 && !c.dlog && full) launch(I128{}, L1{}, Y{}, Y{}, N{}, std::max(512u, 2 * block));
-        else if (HAS_LEAN && lean && block <= 128 && !c.dlog) launch(I128{}, L1{}, Y{}, N{}, N{}, std::max(512u, 2 * block));
-        else if (HAS_LEAN && lean && block <= 128 && full) launch(I128{}, L2{}, Y{}, Y{}, N{}, std::max(512u, 2 * block));
-        else if (HAS_LEAN && lean && block <= 128) launch(I128{}, L2{}, Y{}, N{}, N{}, std::max(512u, 2 * block));
-        else launch(I512{}, L0{}, N{}, N{}, N{}, block);
+        if (HAS_LEAN && lean && block <= 128) {
+            if (full && sparse) by_lean([&](auto l) { launch(I128{}, l, Y{}, Y{}, Y{}, 2 * block); });
+            else if (full && light) by_lean([&](auto l) { launch_df(l, Y{}); });
+            else if (light) by_lean([&](auto l) { launch_df(l, N{}); });
+            else if (full) by_lean([&](auto l) { launch(I128{}, l, Y{}, Y{}, N{}, std::max(512u, 2 * block)); });
+            else by_lean([&](auto l) { launch(I128{}, l, Y{}, N{}, N{}, std::max(512u, 2 * block)); });
+        } else {
+            launch(I512{}, L0{}, N{}, N{}, N{}, block);
+        }
     };
     using Yes = std::true_type;
     using No = std::false_type;
@@ -103,4 +91,5 @@ int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& 
     return QE_OK;
 }
 
-template int launch_persistent<QE_INST_T, QE_INST_ENV>(qe_engine*, qe_env*, RolloutSlot&, const Ctx<QE_INST_T>&, const EnvCtx&, int64_t, int);
+template int launch_persistent<QE_INST_T, QE_INST_ENV>(qe_engine*, qe_env*, RolloutSlot&, const Ctx<QE_INST_T>&, const EnvCtx&, int64_t, int,
+                                                       int);

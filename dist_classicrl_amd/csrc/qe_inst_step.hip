@@ -91,72 +91,77 @@ void launch_step(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& e
 }
 
 // Lane-group widths of the BASELINE shapes get kernels with compile-time width (DPP lane exchange
-// instead of ds_bpermute); everything else runs the generic build.
-template <typename T, class Env>
-void launch_step_any(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int flags, bool slow,
-                     int sample = -1) {
+// instead of ds_bpermute); everything else runs the generic build.  f(std::integral_constant<int, LC>{}), LC = 0: generic.
+template <class Env, class F>
+void by_lane_width(int L, F f) {
     if constexpr (std::is_same<Env, HashEnv>::value) {
-        switch (c.L) {
-            case 4: return launch_step<T, Env, 4>(e, sl, c, ev, flags, slow, sample);
-            case 8: return launch_step<T, Env, 8>(e, sl, c, ev, flags, slow, sample);
-            case 16: return launch_step<T, Env, 16>(e, sl, c, ev, flags, slow, sample);
+        switch (L) {
+            case 4: return f(std::integral_constant<int, 4>{});
+            case 8: return f(std::integral_constant<int, 8>{});
+            case 16: return f(std::integral_constant<int, 16>{});
             default: break;
         }
     }
-    launch_step<T, Env, 0>(e, sl, c, ev, flags, slow, sample);
+    f(std::integral_constant<int, 0>{});
+}
+
+template <typename T, class Env>
+void launch_step_any(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int flags, bool slow,
+                     int sample = -1) {
+    by_lane_width<Env>(c.L, [&](auto lc) { launch_step<T, Env, decltype(lc)::value>(e, sl, c, ev, flags, slow, sample); });
 }
 
 // The vector steps of one rollout call: select(0) + env.step(0), `steps - 1` x {learn, select, env.step}, learn(steps - 1).
 template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn) {
-        const int base = FLAG_ACCOUNT;
-        launch_step_any<T, Env>(e, sl, c, ev, base | FLAG_SELECT, false);  // select(0), env.step(0)
-        while ((int)sl.sample_ev.size() < 2 * MAX_SAMPLES) {
-            hipEvent_t evn;
-            HIP_TRY(hipEventCreate(&evn));
-            sl.sample_ev.push_back(evn);
+    const int base = FLAG_ACCOUNT;
+    launch_step_any<T, Env>(e, sl, c, ev, base | FLAG_SELECT, false);  // select(0), env.step(0)
+    while ((int)sl.sample_ev.size() < 2 * MAX_SAMPLES) {
+        hipEvent_t evn;
+        HIP_TRY(hipEventCreate(&evn));
+        sl.sample_ev.push_back(evn);
+    }
+    // The steady-state steps all launch the same kernels with the same arguments (the step index
+    // lives in the control block), so a block of GRAPH_STEPS of them is captured once per call
+    // into a HIP graph and replayed: the host no longer pays one launch per kernel.  The first
+    // steps stay eager so that the dominant kernel can be bracketed by events.
+    // (Turnstile path: its launches do not move the step counter themselves; a launch works on step
+    // counter + turn_t_off, `t_base` is the counter's value in stream order.)
+    int64_t done = 0, t_base = 0;
+    auto at_step = [&](int64_t step) { Ctx<T> cc = c; if (turn) cc.turn_t_off = step - t_base; return cc; };
+    auto bump = [&](int64_t by) {
+        hipLaunchKernelGGL(k_turn_bump, dim3(1), dim3(1), 0, e->stream, sl.ctrl, (long long)by);
+        t_base += by;
+    };
+    const int64_t middle = steps - 1;
+    const int64_t eager_head = std::min<int64_t>(middle, 32);
+    for (; done < eager_head; ++done) {
+        const int sample = sl.n_samples < MAX_SAMPLES ? sl.n_samples++ : -1;
+        launch_step_any<T, Env>(e, sl, at_step(done), ev, base | FLAG_LEARN | FLAG_SELECT, true, sample);
+    }
+    if (e->opt_graph && middle - done >= 2 * GRAPH_STEPS) {
+        if (sl.graph_exec) { (void)hipGraphExecDestroy(sl.graph_exec); sl.graph_exec = nullptr; }
+        if (turn) bump(done - t_base);  // the graph's launches count from the counter
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+        const int64_t before = sl.launches;
+        for (int k = 0; k < GRAPH_STEPS; ++k)
+            launch_step_any<T, Env>(e, sl, at_step(t_base + k), ev, base | FLAG_LEARN | FLAG_SELECT, true);
+        if (turn) hipLaunchKernelGGL(k_turn_bump, dim3(1), dim3(1), 0, e->stream, sl.ctrl, (long long)GRAPH_STEPS);
+        const int64_t per_replay = sl.launches - before;
+        sl.launches = before;
+        HIP_TRY(hipStreamEndCapture(e->stream, &graph));
+        const hipError_t ie = hipGraphInstantiate(&sl.graph_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        HIP_TRY(ie);
+        for (; middle - done >= GRAPH_STEPS; done += GRAPH_STEPS) {
+            HIP_TRY(hipGraphLaunch(sl.graph_exec, e->stream));
+            sl.launches += per_replay;
+            if (turn) t_base += GRAPH_STEPS;
         }
-        // The steady-state steps all launch the same kernels with the same arguments (the step index
-        // lives in the control block), so a block of GRAPH_STEPS of them is captured once per call
-        // into a HIP graph and replayed: the host no longer pays one launch per kernel.  The first
-        // steps stay eager so that the dominant kernel can be bracketed by events.
-        // (Turnstile path: its launches do not move the step counter themselves; a launch works on step
-        // counter + turn_t_off, `t_base` is the counter's value in stream order.)
-        int64_t done = 0, t_base = 0;
-        auto at_step = [&](int64_t step) { Ctx<T> cc = c; if (turn) cc.turn_t_off = step - t_base; return cc; };
-        auto bump = [&](int64_t by) {
-            hipLaunchKernelGGL(k_turn_bump, dim3(1), dim3(1), 0, e->stream, sl.ctrl, (long long)by);
-            t_base += by;
-        };
-        const int64_t middle = steps - 1;
-        const int64_t eager_head = std::min<int64_t>(middle, 32);
-        for (; done < eager_head; ++done) {
-            const int sample = sl.n_samples < MAX_SAMPLES ? sl.n_samples++ : -1;
-            launch_step_any<T, Env>(e, sl, at_step(done), ev, base | FLAG_LEARN | FLAG_SELECT, true, sample);
-        }
-        if (e->opt_graph && middle - done >= 2 * GRAPH_STEPS) {
-            if (sl.graph_exec) { (void)hipGraphExecDestroy(sl.graph_exec); sl.graph_exec = nullptr; }
-            if (turn) bump(done - t_base);  // the graph's launches count from the counter
-            hipGraph_t graph = nullptr;
-            HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-            const int64_t before = sl.launches;
-            for (int k = 0; k < GRAPH_STEPS; ++k)
-                launch_step_any<T, Env>(e, sl, at_step(t_base + k), ev, base | FLAG_LEARN | FLAG_SELECT, true);
-            if (turn) hipLaunchKernelGGL(k_turn_bump, dim3(1), dim3(1), 0, e->stream, sl.ctrl, (long long)GRAPH_STEPS);
-            const int64_t per_replay = sl.launches - before;
-            sl.launches = before;
-            HIP_TRY(hipStreamEndCapture(e->stream, &graph));
-            const hipError_t ie = hipGraphInstantiate(&sl.graph_exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_TRY(ie);
-            for (; middle - done >= GRAPH_STEPS; done += GRAPH_STEPS) {
-                HIP_TRY(hipGraphLaunch(sl.graph_exec, e->stream));
-                sl.launches += per_replay;
-                if (turn) t_base += GRAPH_STEPS;
-            }
-        }
-        for (; done < middle; ++done) launch_step_any<T, Env>(e, sl, at_step(done), ev, base | FLAG_LEARN | FLAG_SELECT, true);
-        launch_step_any<T, Env>(e, sl, at_step(middle), ev, base | FLAG_LEARN, true);  // learn(steps-1)
+    }
+    for (; done < middle; ++done) launch_step_any<T, Env>(e, sl, at_step(done), ev, base | FLAG_LEARN | FLAG_SELECT, true);
+    launch_step_any<T, Env>(e, sl, at_step(middle), ev, base | FLAG_LEARN, true);  // learn(steps-1)
     return QE_OK;
 }
 
@@ -172,16 +177,7 @@ int turn_occupancy(const qe_engine* e) {
         if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_vec, k_step_turn<T, Env, LC, true>, TURN_BLOCK, 0);
         nb = nb_iter < nb_vec ? nb_iter : nb_vec;
     };
-    if constexpr (std::is_same<Env, HashEnv>::value) {  // (same choice as launch_step_any)
-        switch (e->L) {
-            case 4: ask(std::integral_constant<int, 4>{}); break;
-            case 8: ask(std::integral_constant<int, 8>{}); break;
-            case 16: ask(std::integral_constant<int, 16>{}); break;
-            default: ask(std::integral_constant<int, 0>{}); break;
-        }
-    } else {
-        ask(std::integral_constant<int, 0>{});
-    }
+    by_lane_width<Env>(e->L, ask);
     return err == hipSuccess ? nb : 0;
 }
 
