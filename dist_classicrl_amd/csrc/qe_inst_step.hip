@@ -26,64 +26,40 @@ void launch_step(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& e
     if (sample >= 0) (void)hipEventRecord(sl.sample_ev[2 * sample + 1], e->stream);
     ++sl.launches;
     if (!slow) return;
-    if (c.tok && c.mode == QE_LEARN_VEC) {
-        // wide mode, learn_vec: increments of all involved agents from the pre-step table, then rounds that
-        // add them row by row in agent order, the one-workgroup clean-up, postponed selections
+    if (c.tok) {
+        // wide mode: token rounds on the whole chip, the one-workgroup clean-up, postponed selections.
+        // learn_vec first forms the increments of all involved agents from the pre-step table, and its
+        // rounds add them row by row in agent order.  From k_compact's lists when c.pend_list is set.
+        const bool vec = c.mode == QE_LEARN_VEC;
         const int rounds = sl.rounds;
         const dim3 cgrid(grid_for((c.N + 31) / 32, FAST_BLOCK));
         const dim3 lgrid(std::min<unsigned>(grid.x, LISTED_GRID));
-        const int32_t* list0 = c.pend_list;  // nullptr: scan the bitmap
-        int launches = 3;
+        const int32_t* list0 = c.pend_list;  // nullptr: walk the bitmap
+        int launches = rounds + 2;  // + k_step_slow, k_advance
         if (list0) {
             hipLaunchKernelGGL((k_compact<T>), cgrid, block, 0, e->stream, c, (const uint32_t*)c.inv_bitmap, c.pend_list, 0);
             ++launches;
         }
-        hipLaunchKernelGGL((k_vec_inc<T, Env, LC>), list0 ? lgrid : grid, block, 0, e->stream, c, ev, list0);
+        if (vec) {
+            hipLaunchKernelGGL((k_vec_inc<T, Env, LC>), list0 ? lgrid : grid, block, 0, e->stream, c, ev, list0);
+            ++launches;
+        }
         for (int r = 0; r < rounds; ++r) {
             if (list0 && r == LISTED_RECOMPACT) {
                 hipLaunchKernelGGL((k_compact<T>), cgrid, block, 0, e->stream, c, (const uint32_t*)c.inv_bitmap, c.inv_list, 1);
                 ++launches;
             }
-            const bool second = list0 && r >= LISTED_RECOMPACT;
-            hipLaunchKernelGGL((k_vec_round<T>), lgrid, block, 0, e->stream, c, flags, r,
-                               (const int32_t*)(second ? c.inv_list : list0), second ? 1 : 0);
+            const int which = list0 && r >= LISTED_RECOMPACT ? 1 : 0;
+            const int32_t* list = which ? c.inv_list : list0;
+            if (vec) hipLaunchKernelGGL((k_vec_round<T>), lgrid, block, 0, e->stream, c, flags, r, list, which);
+            else if (list0) hipLaunchKernelGGL((k_token_round<T, Env, LC, true>), lgrid, block, 0, e->stream, c, ev, flags, r, list, which);
+            else hipLaunchKernelGGL((k_token_round<T, Env, LC, false>), grid, block, 0, e->stream, c, ev, flags, r, list, which);
         }
         hipLaunchKernelGGL((k_step_slow<T, Env, LC>), dim3(1), dim3(SLOW_BLOCK), 0, e->stream, c, ev,
-                           (flags & ~FLAG_SELECT) | FLAG_VEC_INC_READY);
-        if (list0)
-            hipLaunchKernelGGL((k_advance_list<T, Env, LC>), lgrid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1, list0);
-        else
-            hipLaunchKernelGGL((k_advance<T, Env, LC>), grid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1);
-        sl.launches += rounds + launches;
-        return;
-    }
-    if (c.tok) {  // wide mode: token rounds on the whole chip, clean-up, postponed selections
-        const int rounds = sl.rounds;
-        if (c.pend_list) {
-            const dim3 cgrid(grid_for((c.N + 31) / 32, FAST_BLOCK));
-            const dim3 lgrid(std::min<unsigned>(grid.x, LISTED_GRID));
-            hipLaunchKernelGGL((k_compact<T>), cgrid, block, 0, e->stream, c, (const uint32_t*)c.inv_bitmap, c.pend_list, 0);
-            int launches = 3;
-            for (int r = 0; r < rounds; ++r) {
-                if (r == LISTED_RECOMPACT) {
-                    hipLaunchKernelGGL((k_compact<T>), cgrid, block, 0, e->stream, c, (const uint32_t*)c.inv_bitmap, c.inv_list, 1);
-                    ++launches;
-                }
-                const bool second = r >= LISTED_RECOMPACT;
-                hipLaunchKernelGGL((k_token_round_list<T, Env, LC>), lgrid, block, 0, e->stream, c, ev, flags, r,
-                                   (const int32_t*)(second ? c.inv_list : c.pend_list), second ? 1 : 0);
-            }
-            hipLaunchKernelGGL((k_step_slow<T, Env, LC>), dim3(1), dim3(SLOW_BLOCK), 0, e->stream, c, ev, flags & ~FLAG_SELECT);
-            hipLaunchKernelGGL((k_advance_list<T, Env, LC>), lgrid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1,
-                               (const int32_t*)c.pend_list);
-            sl.launches += rounds + launches;
-            return;
-        }
-        for (int r = 0; r < rounds; ++r)
-            hipLaunchKernelGGL((k_token_round<T, Env, LC>), grid, block, 0, e->stream, c, ev, flags, r);
-        hipLaunchKernelGGL((k_step_slow<T, Env, LC>), dim3(1), dim3(SLOW_BLOCK), 0, e->stream, c, ev, flags & ~FLAG_SELECT);
-        hipLaunchKernelGGL((k_advance<T, Env, LC>), grid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1);
-        sl.launches += rounds + 2;
+                           (flags & ~FLAG_SELECT) | (vec ? FLAG_VEC_INC_READY : 0));
+        if (list0) hipLaunchKernelGGL((k_advance<T, Env, LC, true>), lgrid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1, list0);
+        else hipLaunchKernelGGL((k_advance<T, Env, LC, false>), grid, block, 0, e->stream, c, ev, flags | FLAG_T_MINUS_1, list0);
+        sl.launches += launches;
         return;
     }
     hipLaunchKernelGGL((k_step_slow<T, Env, LC>), dim3(1), dim3(SLOW_BLOCK), 0, e->stream, c, ev, flags);

@@ -15,7 +15,7 @@
 //                    order (learn_vec / np.add.at, :819-891).
 //   wide mode (>= 2048 agents): k_token_round x R between the two works most involved agents off on
 //                    the whole chip (lowest pending toucher of every row goes first), k_advance runs
-//                    the selections that had to wait for them; k_compact / *_list walk compacted lists.
+//                    the selections that had to wait for them; from k_compact's lists at large N.
 //   k_rollout_lane (qe_rollout_lane.h): <= 512 agents, <= 64 actions -- the whole loop in ONE launch on one
 //                    CU, one agent per lane, contention tracked in LDS, one workgroup barrier per quiet step.
 //
@@ -485,27 +485,8 @@ __device__ __forceinline__ LiveAgent<T> live_agent(const Ctx<T>& c, int64_t i) {
     return g;
 }
 
-// learn(t) for one involved agent; all L lanes of a group call it.
-template <typename T, class Env, int LC = 0>
-__device__ __forceinline__ void ordered_learn(const Ctx<T>& c, const EnvCtx& ev, int64_t i, int sub,
-                                              long long t) {
-    const LiveAgent<T> g = live_agent(c, i);
-    T m = 0;
-    if (!g.term) {
-        const Row4<T> row = load_row4(c.q, g.n, c.ld, sub);
-        m = row_max_valid<LC>(row, Env::valid4(ev, i, g.n, sub), c.L);
-    }
-    if (sub == 0) {
-        const int64_t cell = (int64_t)g.s * c.ld + g.a;
-        const T q0 = c.q[cell];
-        T u;
-        c.q[cell] = Td<T>::apply(q0, g.r, m, g.term, make_hyper(c, c.lr[t]), 0, &u);
-        log_delta(c, t, i, cell, u);
-    }
-}
-
-// The same for the involved agent staged at list position `pos`: the transition comes from the LDS
-// staging area (nothing is read from the agent arrays), rows and cell from the table.
+// learn(t) for the involved agent staged at list position `pos`; all L lanes of a group call it.  The
+// transition comes from the LDS staging area (nothing is read from the agent arrays), rows and cell from the table.
 template <typename T, class Env, int LC = 0, class Lds>
 __device__ __forceinline__ void ordered_learn_staged(const Ctx<T>& c, const EnvCtx& ev, Lds& lds, int pos, int sub,
                                                      long long t) {
@@ -1034,21 +1015,11 @@ __device__ __forceinline__ void token_round_agent(const Ctx<T>& c, const EnvCtx&
     }
 }
 
-template <typename T, class Env, int LC = 0>
-__global__ __launch_bounds__(FAST_BLOCK) void k_token_round(Ctx<T> c, EnvCtx ev, int flags, int round) {
-    const int64_t gl = (int64_t)blockIdx.x * FAST_BLOCK + threadIdx.x;
-    const int64_t i = gl >> c.lshift;
-    const int sub = (int)(gl & (c.L - 1));
-    if (i >= c.N) return;
-    if (!((c.inv_bitmap[i >> 5] >> (i & 31)) & 1u)) return;  // not pending (whole lane group leaves)
-    token_round_agent<T, Env, LC>(c, ev, flags, round, i, sub, c.ctrl->t_local);
-}
-
 // At large N a round that scans every agent costs more than the work of the few that are still
 // pending.  k_compact turns a bitmap (all involved agents after k_step_fast; the still-pending ones
-// a few rounds later) into a list, and the listed variants of the round / of the postponed selection
-// walk that list with a fixed, modest grid (grid-stride).  Stale entries of a list (agents that have
-// finished since it was built) are skipped by their bitmap bit.
+// a few rounds later) into a list, and the rounds / the postponed selections walk that list with a
+// fixed, modest grid (grid-stride).  Stale entries of a list (agents that have finished since it was
+// built) are skipped by their bitmap bit.
 template <typename T>
 __global__ __launch_bounds__(FAST_BLOCK) void k_compact(Ctx<T> c, const uint32_t* bitmap, int32_t* list, int which) {
     __shared__ int scan[18];
@@ -1072,17 +1043,29 @@ __global__ __launch_bounds__(FAST_BLOCK) void k_compact(Ctx<T> c, const uint32_t
     }
 }
 
-template <typename T, class Env, int LC = 0>
-__global__ __launch_bounds__(FAST_BLOCK) void k_token_round_list(Ctx<T> c, EnvCtx ev, int flags, int round,
-                                                                 const int32_t* list, int which) {
-    const int count = (int)c.ctrl->pend_count[which];
-    const int gpb = FAST_BLOCK >> c.lshift;  // lane groups per block
-    const int sub = (int)(threadIdx.x & (c.L - 1));
-    const long long t = c.ctrl->t_local;
-    for (int p = (int)blockIdx.x * gpb + (int)(threadIdx.x >> c.lshift); p < count; p += (int)gridDim.x * gpb) {
-        const int64_t i = list[p];
-        if (!((c.inv_bitmap[i >> 5] >> (i & 31)) & 1u)) continue;
-        token_round_agent<T, Env, LC>(c, ev, flags, round, i, sub, t);
+// One round over the pending agents (bitmap bit set).  LISTED: those of list[0..pend_count[which]), grid-stride;
+// otherwise one lane group per agent, the grid covering all N.  The walk is a template parameter rather than a
+// run-time choice: one kernel for both would carry the listed loop's registers and set-up into the unlisted walk.
+template <typename T, class Env, int LC, bool LISTED>
+__global__ __launch_bounds__(FAST_BLOCK) void k_token_round(Ctx<T> c, EnvCtx ev, int flags, int round,
+                                                            const int32_t* list, int which) {
+    if constexpr (LISTED) {
+        const int count = (int)c.ctrl->pend_count[which];
+        const int gpb = FAST_BLOCK >> c.lshift;  // lane groups per block
+        const int sub = (int)(threadIdx.x & (c.L - 1));
+        const long long t = c.ctrl->t_local;
+        for (int p = (int)blockIdx.x * gpb + (int)(threadIdx.x >> c.lshift); p < count; p += (int)gridDim.x * gpb) {
+            const int64_t i = list[p];
+            if (!((c.inv_bitmap[i >> 5] >> (i & 31)) & 1u)) continue;
+            token_round_agent<T, Env, LC>(c, ev, flags, round, i, sub, t);
+        }
+    } else {
+        const int64_t gl = (int64_t)blockIdx.x * FAST_BLOCK + threadIdx.x;
+        const int64_t i = gl >> c.lshift;
+        const int sub = (int)(gl & (c.L - 1));
+        if (i >= c.N) return;
+        if (!((c.inv_bitmap[i >> 5] >> (i & 31)) & 1u)) return;  // not pending (whole lane group leaves)
+        token_round_agent<T, Env, LC>(c, ev, flags, round, i, sub, c.ctrl->t_local);
     }
 }
 
@@ -1175,26 +1158,25 @@ __device__ __forceinline__ void advance_postponed(const Ctx<T>& c, const EnvCtx&
     }
 }
 
-template <typename T, class Env, int LC = 0>
-__global__ __launch_bounds__(FAST_BLOCK) void k_advance(Ctx<T> c, EnvCtx ev, int flags) {
-    const int64_t gl = (int64_t)blockIdx.x * FAST_BLOCK + threadIdx.x;
-    const int64_t i = gl >> c.lshift;
-    const int sub = (int)(gl & (c.L - 1));
-    if (i >= c.N) return;
-    if (!((c.adv_bitmap[i >> 5] >> (i & 31)) & 1u)) return;
-    advance_postponed<T, Env, LC>(c, ev, flags, i, sub, c.ctrl->t_local - ((flags & FLAG_T_MINUS_1) ? 1 : 0));
-}
-
-// Listed variant: the first pending list of the step holds exactly the agents whose selection was
-// postponed.  The last block to leave resets the list counters for the next step.
-template <typename T, class Env, int LC = 0>
-__global__ __launch_bounds__(FAST_BLOCK) void k_advance_list(Ctx<T> c, EnvCtx ev, int flags, const int32_t* list) {
-    const int count = (int)c.ctrl->pend_count[0];
-    const int gpb = FAST_BLOCK >> c.lshift;
-    const int sub = (int)(threadIdx.x & (c.L - 1));
-    const long long t = c.ctrl->t_local - ((flags & FLAG_T_MINUS_1) ? 1 : 0);
-    for (int p = (int)blockIdx.x * gpb + (int)(threadIdx.x >> c.lshift); p < count; p += (int)gridDim.x * gpb)
-        advance_postponed<T, Env, LC>(c, ev, flags, list[p], sub, t);
+// The same two walks.  LISTED: the first pending list of the step, which holds exactly the agents whose
+// selection was postponed (every entry is taken); otherwise the agents whose adv_bitmap bit is set.
+template <typename T, class Env, int LC, bool LISTED>
+__global__ __launch_bounds__(FAST_BLOCK) void k_advance(Ctx<T> c, EnvCtx ev, int flags, const int32_t* list) {
+    if constexpr (LISTED) {
+        const int count = (int)c.ctrl->pend_count[0];
+        const int gpb = FAST_BLOCK >> c.lshift;
+        const int sub = (int)(threadIdx.x & (c.L - 1));
+        const long long t = c.ctrl->t_local - ((flags & FLAG_T_MINUS_1) ? 1 : 0);
+        for (int p = (int)blockIdx.x * gpb + (int)(threadIdx.x >> c.lshift); p < count; p += (int)gridDim.x * gpb)
+            advance_postponed<T, Env, LC>(c, ev, flags, list[p], sub, t);
+    } else {
+        const int64_t gl = (int64_t)blockIdx.x * FAST_BLOCK + threadIdx.x;
+        const int64_t i = gl >> c.lshift;
+        const int sub = (int)(gl & (c.L - 1));
+        if (i >= c.N) return;
+        if (!((c.adv_bitmap[i >> 5] >> (i & 31)) & 1u)) return;
+        advance_postponed<T, Env, LC>(c, ev, flags, i, sub, c.ctrl->t_local - ((flags & FLAG_T_MINUS_1) ? 1 : 0));
+    }
 }
 
 // -------------------------------------------------------------------------------------------------
