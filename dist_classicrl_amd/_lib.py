@@ -40,7 +40,7 @@ def decode_variant(v: int) -> dict:
     """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h)."""
     v = int(v)
     return {
-        "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval"}.get(v & 15, "none"),
+        "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population"}.get(v & 15, "none"),
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
         "cap512": bool((v >> 9) & 1), "dataflow": bool((v >> 10) & 1), "nv": (v >> 12) & 255, "masked": bool((v >> 20) & 1),
     }
@@ -115,6 +115,13 @@ class RolloutStats(C.Structure):
     ]
 
 
+class RunSchedule(C.Structure):
+    """``qe_run_schedule``: one run's schedule of a population, as the kernel advances it once per step."""
+
+    _fields_ = [("value", C.c_double), ("min_value", C.c_double), ("factor", C.c_double), ("kind", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _I32P = C.POINTER(C.c_int32)
 _U32P = C.POINTER(C.c_uint32)
@@ -168,6 +175,13 @@ PROTOTYPES = {
     "qe_delta_apply_skip_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64]),
     "qe_delta_apply_sorted_dev": (C.c_int, [_P, _P, C.c_int64]),
     "qe_delta_apply_gathered_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "qe_create_population": (C.c_int, [C.POINTER(_P), C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_int32]),
+    "qe_population_runs": (C.c_int64, [_P]),
+    "qe_population_configure": (C.c_int, [_P, C.POINTER(RunSchedule), C.POINTER(RunSchedule), _F64P]),
+    "qe_population_schedules": (C.c_int, [_P, _F64P, _F64P]),
+    "qe_population_rollout": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(RolloutStats), _I64P, _F32P,
+                                          _I32P, _U32P, _F32P, _U32P]),
+    "qe_population_log": (C.c_int64, [_P, C.c_int64, _I32P, _F32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_replay_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "qe_replay_destroy": (C.c_int, [_P]),

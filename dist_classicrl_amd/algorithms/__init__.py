@@ -1,0 +1,3 @@
+from dist_classicrl_amd.algorithms.population import PopulationRun, QLearningPopulation
+
+__all__ = ["PopulationRun", "QLearningPopulation"]

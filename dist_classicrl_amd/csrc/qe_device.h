@@ -46,6 +46,15 @@ __host__ __device__ __forceinline__ uint32_t mulhi32(uint32_t a, uint32_t b) {
     return (uint32_t)(((uint64_t)a * b) >> 32);
 }
 
+// Exploration rate -> threshold of the first draw word: explore <=> x0 < threshold (oracle/draws.py).  Host (the
+// schedule values of a rollout) and device (the population kernel, which advances its schedules itself).
+__host__ __device__ inline unsigned long long eps_threshold(double eps) {
+    if (!(eps > 0.0)) return 0ull;
+    if (eps >= 1.0) return 1ull << 32;
+    const double v = ceil(eps * 4294967296.0);
+    return v >= 4294967296.0 ? (1ull << 32) : (unsigned long long)v;
+}
+
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 struct Row4 {

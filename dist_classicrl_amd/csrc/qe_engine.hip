@@ -71,13 +71,6 @@ int lanes_per_row(int ld) {  // smallest power of two L with 4*L >= ld
 
 namespace {
 
-unsigned long long eps_threshold(double eps) {
-    if (!(eps > 0.0)) return 0ull;
-    if (eps >= 1.0) return 1ull << 32;
-    const double v = std::ceil(eps * 4294967296.0);
-    return v >= 4294967296.0 ? (1ull << 32) : (unsigned long long)v;
-}
-
 // A freshly page-locked buffer costs ~8 ms on its first DMA of more than a few KB (the runtime maps it
 // for the copy engine lazily; measured: 7.6 ms, then 27 us).  Pay that when the buffer is allocated --
 // engine start-up or a growth step -- not in the middle of somebody's first long rollout: one copy in
@@ -729,12 +722,14 @@ int qe_destroy(qe_engine* e) {
     if (e->replay) e->replay->attached = nullptr;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    for (qe_env* env : e->envs) env->e = nullptr;  // environments that outlive their engine (garbage-collection order)
     if (e->q) (void)hipFree(e->q);
     if (e->stamps) (void)hipFree(e->stamps);
     if (e->ctrl) (void)hipFree(e->ctrl);
     if (e->tok) (void)hipFree(e->tok);
     e->turn_rows.release();
     e->slots[0].release(); e->slots[1].release();
+    e->pop.release();
     if (e->plan_ready) (void)hipEventDestroy(e->plan_ready);
     e->plan_thr.release(); e->plan_lr.release(); e->h_plan_thr.release(); e->h_plan_lr.release();
     e->h_stage.release(); e->warm_scratch.release();
@@ -905,6 +900,7 @@ struct Stager {
 
 int qe_choose_actions(qe_engine* e, const int32_t* states, int64_t n, const uint8_t* masks, double eps,
                       int32_t deterministic, int32_t* out) {
+    if (int rc = not_on_population(e, "qe_choose_actions")) return rc;
     if (n < 0 || (n > 0 && (!states || !out))) return qe_fail(QE_ERR_INVALID, "bad argument");
     if (n == 0) { e->step_ctr += 1; return QE_OK; }
     if (int rc = check_indices(states, n, e->S, "states")) return rc;
@@ -997,6 +993,7 @@ static int learn_launch(qe_engine* e, int64_t n, double lr, bool masked, int32_t
 int qe_learn(qe_engine* e, const int32_t* states, const int32_t* actions, const float* rewards,
              const int32_t* next_states, const uint8_t* terminated, int64_t n, double lr,
              const uint8_t* next_masks, int32_t mode) {
+    if (int rc = not_on_population(e, "qe_learn")) return rc;
     if (n == 0) return QE_OK;
     if (n < 0 || !states || !actions || !rewards || !next_states || !terminated)
         return qe_fail(QE_ERR_INVALID, "bad argument");
@@ -1036,20 +1033,24 @@ int qe_env_create(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p)
     if (!out || !e || !p || N <= 0) return qe_fail(QE_ERR_INVALID, "bad argument");
     *out = nullptr;
     if (e->ld > 256) return qe_fail(QE_ERR_UNSUPPORTED, "device environments support action_size <= 256");
+    if (e->pop.runs && N != e->pop.runs)
+        return qe_fail(QE_ERR_INVALID, "a population of %lld runs needs an environment of %lld agents (have %lld)",
+                       (long long)e->pop.runs, (long long)e->pop.runs, (long long)N);
+    const int64_t S = env_states(e);
     switch (p->kind) {
         case QE_ENV_HASH:
             if (p->p_term_256 < 0 || p->p_term_256 > 256) return qe_fail(QE_ERR_INVALID, "p_term_256 out of range");
             break;
         case QE_ENV_GRID:
-            if (p->side < 2 || (int64_t)p->side * p->side != e->S || e->A != 4)
+            if (p->side < 2 || (int64_t)p->side * p->side != S || e->A != 4)
                 return qe_fail(QE_ERR_INVALID, "GridLake needs state_size == side*side and action_size == 4");
             break;
         case QE_ENV_BANDIT:
-            if (e->S != 1 || e->A != 2 || p->episode_len <= 0)
+            if (S != 1 || e->A != 2 || p->episode_len <= 0)
                 return qe_fail(QE_ERR_INVALID, "bandit needs state_size 1, action_size 2, episode_len > 0");
             break;
         case QE_ENV_TICTACTOE:
-            if (e->S != 19683 || e->A != 9)
+            if (S != 19683 || e->A != 9)
                 return qe_fail(QE_ERR_INVALID, "TicTacToe needs state_size 19683 (3^9) and action_size 9");
             break;
         case QE_ENV_TABLE: return qe_fail(QE_ERR_INVALID, "table environments are created with qe_env_create_table");
@@ -1067,21 +1068,25 @@ int qe_env_create_table(qe_env** out, qe_engine* e, int64_t N, const qe_env_para
     *out = nullptr;
     if (e->ld > 256) return qe_fail(QE_ERR_UNSUPPORTED, "device environments support action_size <= 256");
     if (p->kind != QE_ENV_TABLE) return qe_fail(QE_ERR_INVALID, "qe_env_create_table needs kind QE_ENV_TABLE");
+    if (e->pop.runs && N != e->pop.runs)
+        return qe_fail(QE_ERR_INVALID, "a population of %lld runs needs an environment of %lld agents (have %lld)",
+                       (long long)e->pop.runs, (long long)e->pop.runs, (long long)N);
+    const int64_t S = env_states(e);
     if (t->k < 1 || t->k > 8) return qe_fail(QE_ERR_INVALID, "k = %d outcome slots: must be 1 .. 8", (int)t->k);
-    if (t->n_start < 1 || t->n_start > e->S) return qe_fail(QE_ERR_INVALID, "n_start = %d: must be 1 .. state_size", (int)t->n_start);
+    if (t->n_start < 1 || t->n_start > S) return qe_fail(QE_ERR_INVALID, "n_start = %d: must be 1 .. state_size", (int)t->n_start);
     if (!t->thr || !t->next_state || !t->reward || !t->terminated || !t->start_thr || !t->start_state)
         return qe_fail(QE_ERR_INVALID, "table arrays must not be NULL (masks may)");
-    const uint64_t cells = (uint64_t)e->S * (uint64_t)e->A, recs = cells * (uint64_t)t->k;
+    const uint64_t cells = (uint64_t)S * (uint64_t)e->A, recs = cells * (uint64_t)t->k;
     if (recs > 0x80000000ull) return qe_fail(QE_ERR_INVALID, "state_size * action_size * k = %llu outcome records: at most 2^31",
                                              (unsigned long long)recs);
     for (uint64_t j = 0; j < recs; ++j)
-        if (t->next_state[j] < 0 || t->next_state[j] >= e->S)
+        if (t->next_state[j] < 0 || t->next_state[j] >= S)
             return qe_fail(QE_ERR_INDEX, "next_state[%llu] = %d is out of range [0, %lld)", (unsigned long long)j,
-                           (int)t->next_state[j], (long long)e->S);
+                           (int)t->next_state[j], (long long)S);
     for (int j = 0; j < t->n_start; ++j) {
-        if (t->start_state[j] < 0 || t->start_state[j] >= e->S)
+        if (t->start_state[j] < 0 || t->start_state[j] >= S)
             return qe_fail(QE_ERR_INDEX, "start_state[%d] = %d is out of range [0, %lld)", j, (int)t->start_state[j],
-                           (long long)e->S);
+                           (long long)S);
         if (j > 0 && t->start_thr[j] < t->start_thr[j - 1])
             return qe_fail(QE_ERR_INVALID, "start_thr must be non-decreasing (entry %d)", j);
     }
@@ -1100,7 +1105,7 @@ int qe_env_create_table(qe_env** out, qe_engine* e, int64_t N, const qe_env_para
     std::vector<uint32_t> start((size_t)t->n_start * 2);
     for (int j = 0; j < t->n_start; ++j) { start[2 * j] = t->start_thr[j]; start[2 * j + 1] = (uint32_t)t->start_state[j]; }
     std::vector<uint32_t> maskw;
-    if (t->masks) pack_masks(t->masks, e->S, e->A, maskw);
+    if (t->masks) pack_masks(t->masks, S, e->A, maskw);
     HIP_TRY(hipSetDevice(e->device));
     qe_env_params q = *p;
     q.masked = t->masks ? 1 : 0;
@@ -1129,7 +1134,8 @@ int qe_env_create_table(qe_env** out, qe_engine* e, int64_t N, const qe_env_para
 // The per-agent device state of an environment (no reset yet).
 static int env_alloc(qe_env** out, qe_engine* e, int64_t N, const qe_env_params* p) {
     qe_env* env = new qe_env();
-    env->e = e; env->p = *p; env->N = N;
+    env->e = e; env->device = e->device; env->p = *p; env->N = N;
+    e->envs.push_back(env);
     const size_t un = (size_t)N;
     hipError_t err = env->s.ensure(un);
     if (err == hipSuccess) err = env->a.ensure(un);
@@ -1161,8 +1167,11 @@ static int env_alloc(qe_env** out, qe_engine* e, int64_t N, const qe_env_params*
 
 int qe_env_destroy(qe_env* env) {
     if (!env) return QE_OK;
-    (void)hipSetDevice(env->e->device);
-    (void)hipStreamSynchronize(env->e->stream);
+    (void)hipSetDevice(env->device);
+    if (qe_engine* e = env->e) {  // (an engine destroyed first has drained its stream and forgotten the environment)
+        (void)hipStreamSynchronize(e->stream);
+        e->envs.erase(std::remove(e->envs.begin(), e->envs.end(), env), e->envs.end());
+    }
     env->s.release(); env->a.release(); env->n.release(); env->list.release(); env->pend_list.release(); env->r.release();
     env->acc.release(); env->term.release(); env->pred.release(); env->aux.release();
     env->bitmap.release(); env->adv_bitmap.release(); env->turn_next.release(); env->masks.release(); env->vinc.release();
@@ -1225,7 +1234,7 @@ int qe_env_restore(qe_env* env, const int32_t* obs, const uint32_t* aux, const f
     HIP_TRY(hipSetDevice(e->device));
     env_touched(env);
     if (obs) {
-        if (int rc = check_indices(obs, env->N, e->S, "obs")) return rc;
+        if (int rc = check_indices(obs, env->N, env_states(e), "obs")) return rc;
         HIP_TRY(hipMemcpyAsync(env->n.p, obs, env->N * 4, hipMemcpyHostToDevice, e->stream));
     }
     if (aux) HIP_TRY(hipMemcpyAsync(env->aux.p, aux, env->N * 4, hipMemcpyHostToDevice, e->stream));
@@ -1270,6 +1279,7 @@ int qe_env_step(qe_env* env, const int32_t* actions, int32_t* obs, float* reward
 static int begin(qe_engine* e, qe_env* env, int64_t steps, const double* eps, const double* lr, int mode,
                  int learn, int32_t* trace, int slot) {
     if (!e || !env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
+    if (int rc = not_on_population(e, learn ? "the rollout" : "qe_evaluate")) return rc;
     if (slot < 0 || slot > 1) return qe_fail(QE_ERR_INVALID, "slot must be 0 or 1");
     if (steps <= 0) return qe_fail(QE_ERR_INVALID, "steps must be > 0");
     const bool use_plan = learn && !eps && !lr;
@@ -1303,6 +1313,7 @@ int qe_rollout_begin(qe_engine* e, qe_env* env, int64_t steps, const double* eps
 
 int qe_schedule_plan(qe_engine* e, const double* eps, const double* lr, int64_t count) {
     if (!e || count < 0 || (count > 0 && (!eps || !lr))) return qe_fail(QE_ERR_INVALID, "bad argument");
+    if (int rc = not_on_population(e, "qe_schedule_plan")) return rc;
     if (e->slots[0].busy || e->slots[1].busy) return qe_fail(QE_ERR_INVALID, "a rollout is in flight");
     HIP_TRY(hipSetDevice(e->device));
     // (no rollout in flight = every kernel that read the previous plan has completed: qe_rollout_end
@@ -1324,6 +1335,7 @@ int qe_schedule_plan(qe_engine* e, const double* eps, const double* lr, int64_t 
 
 int64_t qe_rollout_chunk_limit(qe_engine* e, qe_env* env, int32_t learn) {
     if (!e || !env) return 0;
+    if (int rc = not_on_population(e, "qe_rollout_chunk_limit")) return rc;
     // worst case: every agent finishes an episode in every step.  The persistent kernel writes one linear log (the
     // path rollout_path takes first; asked without the turnstile's occupancy query, which the answer does not need)
     if (persistent_path(e, env, learn)) return std::max<int64_t>(1, (e->opt_host_block ? HOST_LOG_CAP : e->ep_cap) / env->N);
@@ -1398,6 +1410,7 @@ int64_t qe_episode_log(qe_engine* e, int64_t cap, int32_t* step, int32_t* agent,
 
 // ---- multi-GPU replica sync --------------------------------------------------------------------
 int qe_delta_log_attach(qe_engine* e, void* dev_buf, int64_t capacity) {
+    if (int rc = not_on_population(e, "the delta log")) return rc;
     if (e->dtype != QE_F32 && dev_buf) return qe_fail(QE_ERR_UNSUPPORTED, "delta log needs a float32 table");
     e->dlog = (DeltaEntry*)dev_buf;
     e->dlog_cap = dev_buf ? capacity : 0;
@@ -1408,6 +1421,7 @@ int64_t qe_delta_log_count(qe_engine* e) { return e->dlog_count; }
 int qe_delta_log_reset(qe_engine* e) { e->dlog_count = 0; return QE_OK; }
 
 int qe_delta_apply_dev(qe_engine* e, const void* dev_entries, int64_t count) {
+    if (int rc = not_on_population(e, "qe_delta_apply_dev")) return rc;
     if (count <= 0) return QE_OK;
     if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     HIP_TRY(hipSetDevice(e->device));
@@ -1419,6 +1433,7 @@ int qe_delta_apply_dev(qe_engine* e, const void* dev_entries, int64_t count) {
 
 int qe_delta_apply_skip_dev(qe_engine* e, const void* dev_entries, int64_t count, int64_t skip_begin,
                             int64_t skip_end) {
+    if (int rc = not_on_population(e, "qe_delta_apply_skip_dev")) return rc;
     if (!e || skip_begin < 0 || skip_end < skip_begin || skip_end > count) return qe_fail(QE_ERR_INVALID, "bad argument");
     const int64_t live = count - (skip_end - skip_begin);
     if (live <= 0) return QE_OK;
@@ -1431,6 +1446,7 @@ int qe_delta_apply_skip_dev(qe_engine* e, const void* dev_entries, int64_t count
 }
 
 int qe_delta_apply_sorted_dev(qe_engine* e, const void* dev_entries, int64_t count) {
+    if (int rc = not_on_population(e, "qe_delta_apply_sorted_dev")) return rc;
     if (count <= 0) return QE_OK;
     if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     HIP_TRY(hipSetDevice(e->device));
@@ -1442,6 +1458,7 @@ int qe_delta_apply_sorted_dev(qe_engine* e, const void* dev_entries, int64_t cou
 
 int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t capacity, int64_t count, int32_t world,
                                 int32_t rank) {
+    if (int rc = not_on_population(e, "qe_delta_apply_gathered_dev")) return rc;
     if (!e || !gathered_dev || capacity <= 0 || count < 0 || count > capacity || world < 1 || rank < 0 || rank >= world)
         return qe_fail(QE_ERR_INVALID, "bad argument");
     const int64_t n = (int64_t)(world - 1) * count;
@@ -1567,6 +1584,7 @@ int qe_replay_push(qe_replay* rb, const int64_t* states, const int64_t* actions,
 }
 
 int qe_replay_attach(qe_engine* e, qe_replay* rb) {
+    if (int rc = not_on_population(e, "qe_replay_attach")) return rc;
     if (!e) return qe_fail(QE_ERR_INVALID, "engine is NULL");
     if (rb && rb->device != e->device) return qe_fail(QE_ERR_INVALID, "replay buffer and engine live on different devices");
     if (e->slots[0].busy || e->slots[1].busy) return qe_fail(QE_ERR_INVALID, "a rollout is in flight");
@@ -1622,6 +1640,7 @@ int qe_replay_gather(qe_replay* rb, const int64_t* indices, int64_t n, int64_t* 
 }
 
 int qe_replay_learn(qe_replay* rb, qe_engine* e, const int64_t* indices, int64_t n, double lr, int32_t mode) {
+    if (int rc = not_on_population(e, "qe_replay_learn")) return rc;
     if (!rb || !e || n < 0 || (n > 0 && !indices)) return qe_fail(QE_ERR_INVALID, "bad argument");
     if (rb->device != e->device) return qe_fail(QE_ERR_INVALID, "replay buffer and engine live on different devices");
     if (mode != QE_LEARN_ITER && mode != QE_LEARN_VEC) return qe_fail(QE_ERR_INVALID, "bad learn mode");

@@ -20,6 +20,7 @@
 
 #include "qe_kernels.h"
 #include "qe_rollout_lane.h"
+#include "qe_rollout_runs.h"
 #include "qe_step_turn.h"
 
 using namespace qe;
@@ -150,6 +151,32 @@ struct RolloutSlot {
 
 struct qe_replay;
 
+// Population engine (qe_create_population): `runs` independent single-agent runs, run r in table rows r*S .. r*S+S-1
+// (k_rollout_runs, qe_population.hip).  runs == 0: an ordinary engine.
+struct PopState {
+    int64_t runs = 0, S = 0;           // runs, states of one run (the engine's S is runs * S: table I/O sees the whole table)
+    DevBuf<RunSched> eps, lr;          // per-run schedule descriptors (their values advance in the kernel)
+    DevBuf<double> gamma;
+    DevBuf<uint32_t> status;           // per run, per call: 1 = some step found no selectable action
+    DevBuf<long long> ep_count;        // per run, per call: episodes ended ...
+    DevBuf<float> ep_sum;              // ... and the float32 sequential sum of their returns
+    DevBuf<int32_t> seg_cnt, seg_step, off, out_step;  // episode log: per-run segments of a launch, compacted copy
+    DevBuf<float> seg_ret, out_ret;
+    PinnedBuf<int32_t> h_cnt, h_step;
+    PinnedBuf<float> h_ret;
+    std::vector<int32_t> log_step;     // episode log of the latest call in (run, episode) order
+    std::vector<float> log_ret;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    void release() {
+        eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
+        seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
+        h_cnt.release(); h_step.release(); h_ret.release();
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ev0 = ev1 = nullptr;
+    }
+};
+
 struct qe_engine {
     qe_replay* replay = nullptr;  // ring the fused rollouts push their transitions into (qe_replay_attach)
     int device = 0;
@@ -220,6 +247,8 @@ struct qe_engine {
     DevBuf<uint8_t> warm_scratch;       // 1 MB of device memory for warm_pinned()
     hipStream_t copy_stream = nullptr;  // result read-back beside the compute stream
     RolloutSlot slots[2];               // two rollouts may be in flight (begin k+1 before end k)
+    PopState pop;                       // population engine (qe_create_population), else pop.runs == 0
+    std::vector<struct qe_env*> envs;   // environments created on this engine (qe_destroy detaches them)
     size_t esize() const { return dtype == QE_F32 ? 4 : 8; }
 };
 
@@ -236,7 +265,8 @@ struct qe_replay {
 };
 
 struct qe_env {
-    qe_engine* e = nullptr;
+    qe_engine* e = nullptr;  // null once the engine has been destroyed: only qe_env_destroy is valid then
+    int device = 0;
     qe_env_params p{};
     int64_t N = 0;
     DevBuf<int32_t> s, a, n, list, pend_list;
@@ -255,9 +285,18 @@ struct qe_env {
     const float* mirror_acc = nullptr;
 };
 
+// States an environment of this engine moves in: the table's rows, or those of one run of a population.
+inline int64_t env_states(const qe_engine* e) { return e->pop.runs ? e->pop.S : e->S; }
+
+// Entry points that a population engine does not serve (everything that assumes one table shared by all agents).
+inline int not_on_population(const qe_engine* e, const char* what) {
+    if (e && e->pop.runs) return qe_fail(QE_ERR_UNSUPPORTED, "%s is not available on a population engine (qe_population_rollout)", what);
+    return QE_OK;
+}
+
 inline EnvCtx make_envctx(const qe_engine* e, const qe_env_params* p, const uint32_t* maskbits, int masked) {
     EnvCtx ev{};
-    ev.S = e->S;
+    ev.S = env_states(e);
     ev.A = e->A;
     ev.n_words = (e->A + 31) / 32;
     ev.maskbits = maskbits;
@@ -344,11 +383,12 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   persistent path only: bits 4-5 LEAN (0 generic, 1 plain training rollout, 2 + delta log), bit 6 HELP (draw-producing
 //   wavefronts), bit 7 FULL (every lane an agent), bit 8 SEQ (built without the general ordered path), bit 9 the
 //   512-agent build, bit 10 the dataflow kernel (k_rollout_df), bits 12-19 NV (16-byte loads per fp32 row), bit 20
-//   masked environment
+//   masked environment; path 6 = population (k_rollout_runs) with the same NV and masked bits
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
                   QE_VARIANT_EVAL = (int64_t)RolloutPath::Eval;
+constexpr int64_t QE_VARIANT_RUNS = 6;  // population path (k_rollout_runs): bits 12-19 NV, bit 20 masked, as persistent
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -357,6 +397,9 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
+// population path: one launch of `steps` steps of every run (qe_inst_runs.hip); returns its kernel_variant
+template <typename T, class Env>
+int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps);
 // resident workgroups per CU of the k_step_turn build this engine would launch (occupancy query), 0 on failure
 template <typename T, class Env>
 int turn_occupancy(const qe_engine* e);

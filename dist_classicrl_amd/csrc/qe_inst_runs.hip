@@ -1,0 +1,38 @@
+// qe_inst_runs.hip -- population path: the k_rollout_runs instantiations of ONE (table dtype, environment) pair.
+// Compiled once per pair (-DQE_INST_T=... -DQE_INST_ENV=...), see Makefile; qe_population.hip calls launch_runs.
+#include "qe_host.h"
+#include "qe_rollout_runs.h"
+
+#if !defined(QE_INST_T) || !defined(QE_INST_ENV)
+#error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
+#endif
+
+// One launch of `steps` steps of every run; returns the kernel_variant of the build (QE_VARIANT_RUNS | NV | masked).
+template <typename T, class Env>
+int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps) {
+    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
+    auto go = [&](auto nv, auto mk) -> int64_t {
+        constexpr int NV = decltype(nv)::value;
+        constexpr bool MK = decltype(mk)::value;
+        hipLaunchKernelGGL((k_rollout_runs<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps);
+        return QE_VARIANT_RUNS | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    if constexpr (std::is_same<Env, HashEnv>::value || std::is_same<Env, TableEnv>::value) {  // any A, masked or not
+        auto by_mask = [&](auto nv) { return masked ? go(nv, Yes{}) : go(nv, No{}); };
+        switch (ld) {  // a power of two (row_stride), at most 64
+            case 4: return by_mask(std::integral_constant<int, 1>{});
+            case 8: return by_mask(std::integral_constant<int, 2>{});
+            case 16: return by_mask(std::integral_constant<int, 4>{});
+            case 32: return by_mask(std::integral_constant<int, 8>{});
+            default: return by_mask(std::integral_constant<int, 16>{});
+        }
+    } else if constexpr (std::is_same<Env, TttEnv>::value) {
+        return go(std::integral_constant<int, 4>{}, Yes{});  // A = 9 -> row stride 16
+    } else {
+        return go(std::integral_constant<int, 1>{}, No{});  // GridLake (A = 4) and the bandit (A = 2)
+    }
+}
+
+template int64_t launch_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool, long long);

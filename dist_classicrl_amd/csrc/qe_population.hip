@@ -1,0 +1,284 @@
+// qe_population.hip -- host side of the population path (include/qlearn_engine.h, "population"): M independent
+// single-agent runs in one [M * S, ld] table, stepped by k_rollout_runs (qe_rollout_runs.h, instantiated in
+// qe_inst_runs.hip), plus the compaction of the per-run episode-log segments.
+#include "qe_host.h"
+
+namespace {
+
+// One launch covers at most this many env-steps (runs x steps): well under a second at every shape the population is
+// measured at (tools/population_rate.py), so a launch never holds the device for long.
+constexpr long long RUNS_STEP_BUDGET = 1ll << 25;
+// Episode-log entries of one launch: every run gets a segment of one entry per step of the launch (at most one
+// episode ends per step), so the launches of a logged call are at most RUNS_LOG_BUDGET / runs steps long.
+constexpr long long RUNS_LOG_BUDGET = 1ll << 23;
+
+// Exclusive prefix sum of the runs' segment counts of a launch (one workgroup; off[M] = total).
+__global__ __launch_bounds__(1024) void k_runs_log_scan(const int32_t* cnt, int64_t M, int32_t* off) {
+    __shared__ long long part[1024];
+    const int tid = threadIdx.x;
+    const int64_t per = (M + 1023) / 1024;
+    const int64_t b = std::min<int64_t>(M, tid * per), e = std::min<int64_t>(M, b + per);
+    long long mine = 0;
+    for (int64_t k = b; k < e; ++k) mine += cnt[k];
+    part[tid] = mine;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const long long v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    long long run = part[tid] - mine;
+    for (int64_t k = b; k < e; ++k) {
+        off[k] = (int32_t)run;
+        run += cnt[k];
+    }
+    if (tid == 1023) off[M] = (int32_t)part[1023];
+}
+
+// The real entries of every run's segment, packed in run order.
+__global__ __launch_bounds__(256) void k_runs_log_pack(const int32_t* cnt, const int32_t* off, const int32_t* seg_step,
+                                                       const float* seg_ret, long long seg_len, int64_t M, int32_t* out_step,
+                                                       float* out_ret) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= M) return;
+    const int32_t n = cnt[r], o = off[r];
+    for (int32_t k = 0; k < n; ++k) {
+        out_step[o + k] = seg_step[r * seg_len + k];
+        out_ret[o + k] = seg_ret[r * seg_len + k];
+    }
+}
+
+template <class F>
+int64_t by_env(int kind, F f) {
+    switch (kind) {
+        case QE_ENV_HASH: return f(HashEnv{});
+        case QE_ENV_GRID: return f(GridEnv{});
+        case QE_ENV_BANDIT: return f(BanditEnv{});
+        case QE_ENV_TICTACTOE: return f(TttEnv{});
+        case QE_ENV_TABLE: return f(TableEnv{});
+    }
+    return -1;
+}
+
+int need_population(const qe_engine* e) {
+    if (!e) return qe_fail(QE_ERR_INVALID, "engine is NULL");
+    if (!e->pop.runs) return qe_fail(QE_ERR_INVALID, "not a population engine (qe_create_population)");
+    return QE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qe_create_population(qe_engine** out, int64_t runs, int64_t S, int32_t A, uint64_t seed, int32_t dtype, int32_t device) {
+    if (!out) return qe_fail(QE_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (runs <= 0 || S <= 0 || A <= 0) return qe_fail(QE_ERR_INVALID, "runs, state_size and action_size must be positive");
+    if (runs > 0x7FFFFFFF) return qe_fail(QE_ERR_INVALID, "at most 2^31 - 1 runs");
+    if (A > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions (have %d)", (int)A);
+    if ((double)runs * (double)S >= 4294967296.0) return qe_fail(QE_ERR_UNSUPPORTED, "runs * state_size must be < 2^32 rows");
+    qe_engine* e = nullptr;
+    if (int rc = qe_create(&e, runs * S, A, 0.0, seed, dtype, device)) return rc;
+    // (the touch counters serve the paths that order agents sharing a row: not this one)
+    (void)hipFree(e->stamps);
+    e->stamps = nullptr;
+    e->pop.runs = runs;
+    e->pop.S = S;
+    const size_t m = (size_t)runs;
+    hipError_t err = e->pop.eps.ensure(m);
+    if (err == hipSuccess) err = e->pop.lr.ensure(m);
+    if (err == hipSuccess) err = e->pop.gamma.ensure(m);
+    if (err == hipSuccess) err = e->pop.status.ensure(m);
+    if (err == hipSuccess) err = e->pop.ep_count.ensure(m);
+    if (err == hipSuccess) err = e->pop.ep_sum.ensure(m);
+    if (err == hipSuccess) err = hipMemsetAsync(e->pop.eps.p, 0, m * sizeof(RunSched), e->stream);  // constant 0
+    if (err == hipSuccess) err = hipMemsetAsync(e->pop.lr.p, 0, m * sizeof(RunSched), e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(e->pop.gamma.p, 0, m * sizeof(double), e->stream);
+    if (err == hipSuccess) err = hipEventCreate(&e->pop.ev0);
+    if (err == hipSuccess) err = hipEventCreate(&e->pop.ev1);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err != hipSuccess) {
+        const int code = qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "population allocation failed: %s",
+                                 hipGetErrorString(err));
+        qe_destroy(e);
+        return code;
+    }
+    *out = e;
+    return QE_OK;
+}
+
+int64_t qe_population_runs(qe_engine* e) { return e ? e->pop.runs : 0; }
+
+int qe_population_configure(qe_engine* e, const qe_run_schedule* eps, const qe_run_schedule* lr, const double* gamma) {
+    if (int rc = need_population(e)) return rc;
+    static_assert(sizeof(qe_run_schedule) == sizeof(RunSched), "qe_run_schedule and RunSched differ");
+    const size_t m = (size_t)e->pop.runs;
+    for (const qe_run_schedule* d : {eps, lr})
+        for (size_t r = 0; d && r < m; ++r)
+            if (d[r].kind < QE_SCHED_CONSTANT || d[r].kind > QE_SCHED_EXPONENTIAL)
+                return qe_fail(QE_ERR_INVALID, "schedule of run %lld: unknown kind %d", (long long)r, (int)d[r].kind);
+    HIP_TRY(hipSetDevice(e->device));
+    if (eps) HIP_TRY(hipMemcpyAsync(e->pop.eps.p, eps, m * sizeof(RunSched), hipMemcpyHostToDevice, e->stream));
+    if (lr) HIP_TRY(hipMemcpyAsync(e->pop.lr.p, lr, m * sizeof(RunSched), hipMemcpyHostToDevice, e->stream));
+    if (gamma) HIP_TRY(hipMemcpyAsync(e->pop.gamma.p, gamma, m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_schedules(qe_engine* e, double* eps_values, double* lr_values) {
+    if (int rc = need_population(e)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t m = (size_t)e->pop.runs;
+    std::vector<RunSched> h(m);
+    for (auto [dev, dst] : {std::make_pair(e->pop.eps.p, eps_values), std::make_pair(e->pop.lr.p, lr_values)}) {
+        if (!dst) continue;
+        HIP_TRY(hipMemcpyAsync(h.data(), dev, m * sizeof(RunSched), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t r = 0; r < m; ++r) dst[r] = h[r].value;
+    }
+    return QE_OK;
+}
+
+int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t mode, int32_t log, qe_rollout_stats* stats,
+                              int64_t* ep_count, float* ep_sum, int32_t* obs, uint32_t* aux, float* agent_rewards,
+                              uint32_t* status) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    P.log_step.clear();
+    P.log_ret.clear();
+    if (!env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
+    if (steps < 0) return qe_fail(QE_ERR_INVALID, "steps must be >= 0");
+    if (mode != QE_LEARN_ITER && mode != QE_LEARN_VEC) return qe_fail(QE_ERR_INVALID, "bad learn mode");
+    if (e->ld > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions");
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t M = P.runs;
+    const size_t m = (size_t)M;
+    long long per_launch = std::max<long long>(1, RUNS_STEP_BUDGET / M);
+    if (log) per_launch = std::min<long long>(per_launch, std::max<long long>(1, RUNS_LOG_BUDGET / M));
+    if (steps > 0) per_launch = std::min<long long>(per_launch, steps);
+    if (log) {
+        const size_t seg = m * (size_t)per_launch;
+        HIP_TRY(P.seg_cnt.ensure(m)); HIP_TRY(P.off.ensure(m + 1)); HIP_TRY(P.seg_step.ensure(seg)); HIP_TRY(P.seg_ret.ensure(seg));
+        HIP_TRY(P.out_step.ensure(seg)); HIP_TRY(P.out_ret.ensure(seg)); HIP_TRY(P.h_cnt.ensure(m + 1));
+    }
+    env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
+    HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_sum.p, 0, m * sizeof(float), e->stream));
+    // One agent per run: the reference's dispatcher picks the list variants of the selection (they step over a NaN)
+    // except for masked rows of more than 10 actions (q_learning_optimal.py:700, :713; see rollout_ctx)
+    const bool masked = env->p.masked != 0 || env->p.kind == QE_ENV_TICTACTOE;
+    const int nan_select = masked && e->A > 10 ? 1 : 0;
+    const EnvCtx ev = make_envctx(e, env);
+    // launch-major log of the call: per launch, each run's entries in order
+    std::vector<int32_t> cnt_all, step_all;
+    std::vector<float> ret_all;
+    int64_t launches = 0, variant = QE_VARIANT_RUNS;
+    HIP_TRY(hipEventRecord(P.ev0, e->stream));
+    for (long long t = 0; t < steps; t += per_launch) {
+        const long long k = std::min<long long>(per_launch, steps - t);
+        const int64_t v = by_env(env->p.kind, [&](auto tag) -> int64_t {
+            using Env = decltype(tag);
+            auto go = [&](auto tt) -> int64_t {
+                using T = decltype(tt);
+                RunsCtx<T> c{};
+                c.q = (T*)e->q; c.S = P.S; c.M = M;
+                c.obs = env->n.p; c.aux = env->aux.p; c.acc = env->acc.p;
+                c.eps = P.eps.p; c.lr = P.lr.p; c.gamma = P.gamma.p; c.status = P.status.p;
+                c.ep_count = P.ep_count.p; c.ep_sum = P.ep_sum.p;
+                if (log) { c.seg_cnt = P.seg_cnt.p; c.seg_step = P.seg_step.p; c.seg_ret = P.seg_ret.p; c.seg_len = k; }
+                c.seed_lo = (uint32_t)e->seed; c.seed_hi = (uint32_t)(e->seed >> 32);
+                c.mode = mode; c.nan_select = nan_select;
+                c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
+                return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
+            };
+            return e->dtype == QE_F32 ? go(float{}) : go(double{});
+        });
+        if (v < 0) return qe_fail(QE_ERR_INVALID, "unknown env kind %d", (int)env->p.kind);
+        variant = v;
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (log) {
+            hipLaunchKernelGGL(k_runs_log_scan, dim3(1), dim3(1024), 0, e->stream, (const int32_t*)P.seg_cnt.p, M, P.off.p);
+            hipLaunchKernelGGL(k_runs_log_pack, dim3(grid_for(M, 256)), dim3(256), 0, e->stream, (const int32_t*)P.seg_cnt.p,
+                               (const int32_t*)P.off.p, (const int32_t*)P.seg_step.p, (const float*)P.seg_ret.p, (long long)k, M,
+                               P.out_step.p, P.out_ret.p);
+            launches += 2;
+            HIP_TRY(hipMemcpyAsync(P.h_cnt.p, P.seg_cnt.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(P.h_cnt.p + m, P.off.p + m, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            const size_t total = (size_t)P.h_cnt.p[m];
+            cnt_all.insert(cnt_all.end(), P.h_cnt.p, P.h_cnt.p + m);
+            if (total) {
+                HIP_TRY(P.h_step.ensure(total)); HIP_TRY(P.h_ret.ensure(total));
+                HIP_TRY(hipMemcpyAsync(P.h_step.p, P.out_step.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+                HIP_TRY(hipMemcpyAsync(P.h_ret.p, P.out_ret.p, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+                HIP_TRY(hipStreamSynchronize(e->stream));
+                step_all.insert(step_all.end(), P.h_step.p, P.h_step.p + total);
+                ret_all.insert(ret_all.end(), P.h_ret.p, P.h_ret.p + total);
+            }
+        }
+    }
+    HIP_TRY(hipEventRecord(P.ev1, e->stream));
+    e->step_ctr += (uint64_t)steps;
+    std::vector<long long> counts(m);
+    std::vector<uint32_t> st(m);
+    HIP_TRY(hipMemcpyAsync(counts.data(), P.ep_count.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), P.status.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (ep_sum) HIP_TRY(hipMemcpyAsync(ep_sum, P.ep_sum.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (obs) HIP_TRY(hipMemcpyAsync(obs, env->n.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (aux) HIP_TRY(hipMemcpyAsync(aux, env->aux.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (agent_rewards) HIP_TRY(hipMemcpyAsync(agent_rewards, env->acc.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    long long total = 0;
+    for (size_t r = 0; r < m; ++r) {
+        if (ep_count) ep_count[r] = counts[r];
+        total += counts[r];
+    }
+    if (status) memcpy(status, st.data(), m * sizeof(uint32_t));
+    if (log) {  // launch-major -> (run, episode) order
+        std::vector<size_t> at(m + 1, 0);
+        for (size_t r = 0; r < m; ++r) at[r + 1] = at[r] + (size_t)counts[r];
+        P.log_step.resize(step_all.size());
+        P.log_ret.resize(ret_all.size());
+        size_t src = 0;
+        for (size_t l = 0; l < cnt_all.size() / std::max<size_t>(m, 1); ++l)
+            for (size_t r = 0; r < m; ++r)
+                for (int32_t j = 0; j < cnt_all[l * m + r]; ++j, ++src) {
+                    P.log_step[at[r]] = step_all[src];
+                    P.log_ret[at[r]] = ret_all[src];
+                    ++at[r];
+                }
+    }
+    if (stats) {
+        float ms = 0.0f;
+        if (steps > 0) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
+        stats->kernel_ms = ms; stats->launches = launches; stats->episodes = total;
+        stats->dominant_ms = ms; stats->dominant_launches = launches; stats->dominant_env_steps = steps * M;
+        stats->kernel_variant = variant;
+    }
+    for (size_t r = 0; r < m; ++r)
+        if (st[r]) {
+            std::string runs;
+            int named = 0;
+            for (size_t q = r; q < m && named < 8; ++q)
+                if (st[q]) { runs += (named++ ? ", " : "") + std::to_string(q); }
+            return qe_fail(QE_ERR_INDEX, "Cannot choose from an empty sequence (runs %s%s)", runs.c_str(), named == 8 ? ", ..." : "");
+        }
+    return total;
+}
+
+int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret) {
+    if (int rc = need_population(e)) return rc;
+    const int64_t n = (int64_t)e->pop.log_step.size();
+    for (int64_t k = 0; k < n && k < cap; ++k) {
+        if (step) step[k] = e->pop.log_step[(size_t)k];
+        if (ret) ret[k] = e->pop.log_ret[(size_t)k];
+    }
+    return n;
+}
+
+}  // extern "C"

@@ -89,7 +89,8 @@ typedef struct qe_rollout_stats {
                                 2 the same with the delta log), bit 6 draw-producing helper wavefronts, bit 7 every lane an
                                 agent, bit 8 built without the general ordered path ("light"), bit 9 the 512-agent build,
                                 bit 10 the dataflow kernel (sharers of a row ordered by value hand-over in LDS),
-                                bits 12-19 16-byte loads per row, bit 20 masked environment (tests assert on these) */
+                                bits 12-19 16-byte loads per row, bit 20 masked environment (tests assert on these);
+                                path 6: population (qe_population_rollout), with the same NV and masked bits */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -276,6 +277,44 @@ int qe_delta_apply_sorted_dev(qe_engine* e, const void* dev_entries, int64_t cou
  * (Stands in for the parameter server's apply loop, q_learning_async_dist.py:359-447.) */
 int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t capacity, int64_t count, int32_t world,
                                 int32_t rank);
+
+/* ---- population: many independent single-agent runs in one launch ------------------------------------
+ * M runs of the classic one-agent Q-learner (SingleThreadQLearning with one environment, single_thread_runtime.py)
+ * share one MDP and one seed; run r is, bit for bit, the standalone one-agent rollout on the same environment kind with
+ * agent_offset = (the environment's agent_offset) + r, its own schedules and discount.
+ *   qe_create_population  an engine whose table holds runs * state_size rows (run r: rows r*S .. r*S+S-1); its
+ *                         environments (num_agents must equal runs) move in states [0, state_size).  qe_table_upload /
+ *                         qe_table_download[_rows] / qe_table_cells see the whole [runs * S, A] table.  Rows of at
+ *                         most 64 actions (QE_ERR_UNSUPPORTED beyond).  Every rollout, learn, choose, evaluate, replay
+ *                         and delta-log entry point above returns QE_ERR_UNSUPPORTED on it.
+ *   qe_population_configure  per-run schedule descriptors (eps, lr: runs entries each) and discounts (runs doubles);
+ *                         any of the three may be NULL (left as they are; initially constant 0 and discount 0).
+ *   qe_population_schedules  the per-run schedule values now (either pointer may be NULL).
+ *   qe_population_rollout  `steps` steps of every run (schedules advance once per step, as update(1) after each read).
+ *                         Per-run outputs, each `runs` entries, any may be NULL: episodes ended, float32 sequential sum
+ *                         of their returns, observations, env-internal state, running returns, status (1 = some step
+ *                         had no selectable action: the call returns QE_ERR_INDEX after filling the outputs, the other
+ *                         runs are unaffected).  `log` != 0 keeps the episode log of the call (qe_population_log).
+ *                         Returns the number of episodes that ended, or a negative qe_status.
+ *   qe_population_log     the latest call's episode log in (run, episode) order: step within the call and return of
+ *                         the first `cap` entries; returns the count. */
+enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
+typedef struct qe_run_schedule {
+    double value;      /* the value read at the next step */
+    double min_value;  /* EXPONENTIAL: floor, v <- max(v * factor, min_value) */
+    double factor;     /* EXPONENTIAL: decay_rate ** 1; LINEAR: 1 * decay_rate, v <- v + factor */
+    int32_t kind;      /* qe_run_schedule_kind */
+    int32_t reserved;
+} qe_run_schedule;
+int qe_create_population(qe_engine** out, int64_t runs, int64_t state_size, int32_t action_size, uint64_t seed,
+                         int32_t dtype, int32_t device);
+int64_t qe_population_runs(qe_engine* e); /* 0: not a population engine */
+int qe_population_configure(qe_engine* e, const qe_run_schedule* eps, const qe_run_schedule* lr, const double* gamma);
+int qe_population_schedules(qe_engine* e, double* eps_values, double* lr_values);
+int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t mode, int32_t log, qe_rollout_stats* stats,
+                              int64_t* ep_count, float* ep_sum, int32_t* obs, uint32_t* aux, float* agent_rewards,
+                              uint32_t* status);
+int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

@@ -1,0 +1,129 @@
+"""Aggregate env-steps/s of the population path (QLearningPopulation, k_rollout_runs) against the standalone one-agent
+rollout on the same environment, measured in the same process.
+
+    python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick]
+
+Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
+M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
+M = 4096.  Rate = M x steps / wall time of one timed call (after a warm-up call; the call returns after the device has
+finished).  Writes DIR/population_rate.json and prints one line per workload.  For kernel time and bytes per env-step,
+run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/population_rate.py --out DIR --quick`.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+from dist_classicrl_amd.algorithms import QLearningPopulation  # noqa: E402
+from dist_classicrl_amd.algorithms.base_algorithms.q_learning_optimal import OptimalQLearningBase  # noqa: E402
+from dist_classicrl_amd.algorithms.runtime.gpu_rollout_runtime import GpuRolloutQLearning  # noqa: E402
+from dist_classicrl_amd.environments import HashTabularEnv, TabularMDPEnv, TicTacToeEnv  # noqa: E402
+from dist_classicrl_amd.schedules import ExponentialSchedule  # noqa: E402
+
+FROZEN_8x8 = ["SFFFFFFF", "FFFFFFFF", "FFFHFFFF", "FFFFFHFF", "FFFHFFFF", "FHHFFFHF", "FHFFHFHF", "FFFHFFFG"]
+
+
+def frozen_lake_8x8_slippery():
+    """gymnasium's FrozenLake-v1 8x8, is_slippery=True, as a transition dict P[s][a] = [(p, s', r, terminated)]."""
+    n = 8
+    moves = {0: (0, -1), 1: (1, 0), 2: (0, 1), 3: (-1, 0)}  # left, down, right, up
+    P = {}
+    for s in range(n * n):
+        row, col = divmod(s, n)
+        P[s] = {}
+        for a in range(4):
+            out = []
+            for b in ((a - 1) % 4, a, (a + 1) % 4):
+                if FROZEN_8x8[row][col] in "GH":
+                    out.append((1.0 / 3.0, s, 0.0, True))
+                    continue
+                dr, dc = moves[b]
+                r2, c2 = min(max(row + dr, 0), n - 1), min(max(col + dc, 0), n - 1)
+                cell = FROZEN_8x8[r2][c2]
+                out.append((1.0 / 3.0, r2 * n + c2, 1.0 if cell == "G" else 0.0, cell in "GH"))
+            P[s][a] = out
+    isd = np.zeros(n * n)
+    isd[0] = 1.0
+    return P, isd
+
+
+def schedules():
+    return ExponentialSchedule(0.1, 1e-3, 0.9995), ExponentialSchedule(1.0, 0.05, 0.9995)
+
+
+def population_rate(make_env, M, S, A, steps, dtype, log):
+    lr, eps = schedules()
+    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype)
+    env = make_env(M)
+    res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
+    t0 = time.perf_counter()
+    res = pop.run_steps(steps, env, res.state_dict, log=log)
+    wall = time.perf_counter() - t0
+    return {"runs": M, "steps": steps, "wall_s": wall, "env_steps_per_s": M * steps / wall,
+            "kernel_ms": pop.last_stats["kernel_ms"], "launches": int(pop.last_stats["launches"]),
+            "episodes": int(res.episode_counts.sum()), "kernel_variant": int(pop.last_stats["kernel_variant"])}
+
+
+def standalone_rate(make_env, S, A, steps, dtype):
+    lr, eps = schedules()
+    algo = OptimalQLearningBase(S, A, 0.99, seed=1, dtype=dtype)
+    rt = GpuRolloutQLearning(algo, lr, eps)
+    rt.history_type = "array"
+    env = make_env(1)
+    _, _, _, sd = rt.run_steps(min(200, steps), env)
+    t0 = time.perf_counter()
+    rt.run_steps(steps, env, sd)
+    wall = time.perf_counter() - t0
+    return {"steps": steps, "wall_s": wall, "env_steps_per_s": steps / wall}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", required=True, type=Path)
+    ap.add_argument("--steps", type=int, default=10000)
+    ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
+    ap.add_argument("--quick", action="store_true", help="fewer steps and shapes (profiling runs)")
+    args = ap.parse_args()
+    dtype = np.dtype(args.dtype)
+    steps = 1000 if args.quick else args.steps
+    P, isd = frozen_lake_8x8_slippery()
+
+    def lake(n):
+        return TabularMDPEnv.from_transition_dict(P, n, initial_state_distrib=isd, seed=1)
+
+    def ttt(n):
+        return TicTacToeEnv(n, seed=1)
+
+    def hashed(n):
+        return HashTabularEnv(n, 10000, 8, seed=1)
+
+    plan = [("frozenlake8x8", lake, 64, 4, M, steps, log) for M in ((4096, 65536) if args.quick else (64, 1024, 4096, 65536))
+            for log in (True, False)]
+    plan += [("tictactoe", ttt, 19683, 9, 1024, steps // 5, True), ("hash1e4x8", hashed, 10000, 8, 4096, steps, True)]
+    base_cache = {}
+    lines = []
+    for name, make_env, S, A, M, k, log in plan:
+        if name not in base_cache:
+            base_cache[name] = standalone_rate(make_env, S, A, min(k, 5000), dtype)
+        pop = population_rate(make_env, M, S, A, k, dtype, log)
+        base = base_cache[name]
+        line = {"workload": name, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
+                "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
+        lines.append(line)
+        print(f"{name:14s} M={M:6d} log={int(log)} {pop['env_steps_per_s'] / 1e6:10.1f} M env-steps/s "
+              f"(standalone {base['env_steps_per_s'] / 1e6:.3f} M/s, x{line['speedup_vs_standalone']:.0f}; "
+              f"{pop['launches']} launches, kernel {pop['kernel_ms']:.1f} ms)", flush=True)
+    args.out.mkdir(parents=True, exist_ok=True)
+    (args.out / "population_rate.json").write_text(json.dumps(lines, indent=1))
+
+
+if __name__ == "__main__":
+    main()
