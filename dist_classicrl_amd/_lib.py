@@ -40,7 +40,8 @@ def decode_variant(v: int) -> dict:
     """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h)."""
     v = int(v)
     return {
-        "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population"}.get(v & 15, "none"),
+        "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
+                 7: "population_eval"}.get(v & 15, "none"),
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
         "cap512": bool((v >> 9) & 1), "dataflow": bool((v >> 10) & 1), "nv": (v >> 12) & 255, "masked": bool((v >> 20) & 1),
     }
@@ -129,6 +130,7 @@ _U8P = C.POINTER(C.c_uint8)
 _F32P = C.POINTER(C.c_float)
 _F64P = C.POINTER(C.c_double)
 _I64P = C.POINTER(C.c_int64)
+_U64P = C.POINTER(C.c_uint64)
 
 # name -> (restype, argtypes); must list every symbol include/qlearn_engine.h declares
 PROTOTYPES = {
@@ -181,7 +183,11 @@ PROTOTYPES = {
     "qe_population_schedules": (C.c_int, [_P, _F64P, _F64P]),
     "qe_population_rollout": (C.c_int64, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(RolloutStats), _I64P, _F32P,
                                           _I32P, _U32P, _F32P, _U32P]),
+    "qe_population_evaluate": (C.c_int64, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(RolloutStats), _I64P, _F32P,
+                                           _I64P, _U32P]),
     "qe_population_log": (C.c_int64, [_P, C.c_int64, _I32P, _F32P]),
+    "qe_population_step_counters": (C.c_int, [_P, _U64P]),
+    "qe_population_set_step_counters": (C.c_int, [_P, _U64P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_replay_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "qe_replay_destroy": (C.c_int, [_P]),

@@ -1,3 +1,8 @@
-from dist_classicrl_amd.algorithms.population import PopulationRun, QLearningPopulation
+from dist_classicrl_amd.algorithms.population import (
+    PopulationEval,
+    PopulationRun,
+    PopulationTraining,
+    QLearningPopulation,
+)
 
-__all__ = ["PopulationRun", "QLearningPopulation"]
+__all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation"]

@@ -13,6 +13,11 @@ return), the standalone run
 
 where ``env_r`` is the same environment kind and parameters with one agent and ``agent_offset = env_offset + r``.
 Calls chain: one call of 2K steps equals two calls of K steps, schedule values included.
+
+Greedy evaluation (``evaluate_steps`` / ``evaluate_episodes``, kernel ``k_evaluate_runs``) and ``train`` follow the same
+contract: run ``r`` is the standalone runtime's ``evaluate_steps`` / ``evaluate_episodes`` / ``train`` of that one-agent
+run.  Each run keeps its own draw counter (``step_counters``): an episode-based evaluation advances run ``r`` by the
+steps it took, as the standalone ``evaluate_episodes`` does, so later training still draws what the standalone run draws.
 """
 
 from __future__ import annotations
@@ -80,6 +85,34 @@ class PopulationRun(NamedTuple):
         return self.steps[self.offsets[r]:self.offsets[r + 1]]
 
 
+class PopulationEval(NamedTuple):
+    """Result of :meth:`QLearningPopulation.evaluate_steps` / :meth:`~QLearningPopulation.evaluate_episodes`."""
+
+    totals: np.ndarray          # float32 [M]: sequential float32 sum of the run's returns (the standalone sum(history)); 0 if none
+    episode_counts: np.ndarray  # int64 [M]
+    returns: np.ndarray         # float32, every run's returns in order, run after run (empty without the log)
+    offsets: np.ndarray         # int64 [M + 1]: run r's returns are returns[offsets[r]:offsets[r + 1]]
+    steps_used: np.ndarray      # int64 [M]: steps each run took
+    finished: np.ndarray        # bool [M]: episode mode: the run reached its episode count (False: stopped by max_steps)
+
+    def run_returns(self, r: int) -> np.ndarray:
+        return self.returns[self.offsets[r]:self.offsets[r + 1]]
+
+
+class PopulationTraining(NamedTuple):
+    """Result of :meth:`QLearningPopulation.train`."""
+
+    returns: np.ndarray       # float32: every run's training returns of all segments in order, run after run
+    offsets: np.ndarray       # int64 [M + 1]: run r's are returns[offsets[r]:offsets[r + 1]] (its reward_history)
+    val_totals: np.ndarray    # float32 [segments, M]: column r is run r's val_reward_history
+    val_finished: np.ndarray  # bool [segments, M]: PopulationEval.finished of each validation
+    segments: list            # the PopulationRun of each training segment
+    state_dict: dict          # state dict of the last segment
+
+    def run_reward_history(self, r: int) -> np.ndarray:
+        return self.returns[self.offsets[r]:self.offsets[r + 1]]
+
+
 def _per_run(value, runs, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != runs:
@@ -140,12 +173,41 @@ class QLearningPopulation:
 
     @property
     def step_counter(self) -> int:
-        """Index of the next step in the draw protocol (shared by all runs)."""
-        return int(self._lib.qe_get_step_counter(self._h))
+        """Index of the next step in the draw protocol while all runs agree on it (``ValueError`` once an
+        episode-based evaluation has left them apart: see :attr:`step_counters`).  Setting it sets every run's."""
+        counters = self._counters()
+        if (counters != counters[0]).any():
+            msg = "the runs' draw counters differ (after evaluate_episodes): use step_counters"
+            raise ValueError(msg)
+        return int(counters[0])
 
     @step_counter.setter
     def step_counter(self, value: int) -> None:
-        _lib.check(self._lib.qe_set_step_counter(self._h, int(value)))
+        _lib.check(self._lib.qe_set_step_counter(self._h, int(value) & 0xFFFFFFFFFFFFFFFF))
+
+    @property
+    def step_counters(self) -> np.ndarray:
+        """Every run's index of its next step in the draw protocol, int64 ``[runs]`` (the uint64 counters' bits)."""
+        return self._counters().view(np.int64)
+
+    @step_counters.setter
+    def step_counters(self, values) -> None:
+        arr = np.asarray(values)
+        if arr.shape != (self.runs,):
+            msg = f"step_counters: expected {self.runs} entries, got shape {arr.shape}"
+            raise ValueError(msg)
+        arr = np.ascontiguousarray(arr.astype(np.uint64) if arr.dtype.kind == "u" else arr.astype(np.int64).view(np.uint64))
+        _lib.check(self._lib.qe_population_set_step_counters(self._h, _lib.ptr(arr, C.c_uint64)))
+
+    def _counters(self) -> np.ndarray:
+        out = np.empty(self.runs, dtype=np.uint64)
+        _lib.check(self._lib.qe_population_step_counters(self._h, _lib.ptr(out, C.c_uint64)))
+        return out
+
+    def _rng_step(self):
+        """``state_dict["rng_step"]``: an int while all runs agree, else the int64 array of every run's."""
+        counters = self._counters()
+        return int(counters[0]) if (counters == counters[0]).all() else counters.view(np.int64)
 
     # ------------------------------------------------------------------ tables
     @property
@@ -214,9 +276,7 @@ class QLearningPopulation:
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
         result, in which the other runs are unaffected)."""
-        if not isinstance(env, DeviceVecEnv):
-            msg = "a population runs on a device environment (dist_classicrl_amd.environments)"
-            raise TypeError(msg)
+        self._check_env(env)
         steps = int(steps)
         env.bind(self)
         if curr_state_dict is None:
@@ -258,7 +318,7 @@ class QLearningPopulation:
         means[counts == 0] = np.nan
         obs, aux, rewards = state[:M].view(np.int32), state[M:2 * M], state[2 * M:].view(np.float32)
         state_dict = env.adopt_state(obs, rewards, aux)
-        state_dict["rng_step"] = self.step_counter
+        state_dict["rng_step"] = self._rng_step()
         state_dict["lr"] = lr_v
         state_dict["exploration_rate"] = eps_v
         result = PopulationRun(means, counts, rets, offsets, at, state_dict)
@@ -272,13 +332,135 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter and every run's schedule values.  Tables: :meth:`load`; environments: pass the dict to ``run_steps``."""
-        self.step_counter = int(state_dict["rng_step"])
+        counter(s) and every run's schedule values.  Tables: :meth:`load`; environments: pass the dict to ``run_steps``."""
+        rng_step = state_dict["rng_step"]
+        if np.ndim(rng_step) == 0:
+            self.step_counter = int(rng_step)
+        else:
+            self.step_counters = rng_step
         for schedules, key in ((self.lr_schedules, "lr"), (self.exploration_rate_schedules, "exploration_rate")):
             values = np.broadcast_to(np.asarray(state_dict[key], dtype=np.float64), (self.runs,))
             last = {id(s): (s, r) for r, s in enumerate(schedules)}
             for s, r in last.values():
                 s.set_value(float(values[r]))
 
+    # ------------------------------------------------------------------ evaluation and train
+    def _check_env(self, env) -> None:
+        if not isinstance(env, DeviceVecEnv):
+            msg = "a population runs on a device environment (dist_classicrl_amd.environments)"
+            raise TypeError(msg)
+        if env.num_agents != self.runs:
+            msg = f"the environment has {env.num_agents} agents, the population {self.runs} runs: one agent per run"
+            raise ValueError(msg)
 
-__all__ = ["PopulationRun", "QLearningPopulation", "advance_descriptor", "schedule_descriptor"]
+    def evaluate_steps(self, env, steps, log=True) -> PopulationEval:
+        """Greedy evaluation: every run takes ``steps`` steps from ``env.reset(seed=42)`` with its own table, as the
+        standalone one-agent ``evaluate_steps(env_r, steps)``.  Tables and schedules are untouched; every run's draw
+        counter advances by ``steps``.  A run without a selectable action raises ``IndexError`` (``.runs``, ``.result``),
+        as :meth:`run_steps` does."""
+        self._check_env(env)
+        steps = int(steps)
+        if steps < 0:
+            msg = "steps must be >= 0"
+            raise ValueError(msg)
+        return self._evaluate(env, steps, 0, log)
+
+    def evaluate_episodes(self, env, episodes, max_steps=None, log=True) -> PopulationEval:
+        """Greedy evaluation until each run has ended ``episodes`` episodes, as the standalone one-agent
+        ``evaluate_episodes(env_r, episodes)``: run ``r`` stops at the end of the step in which its count is reached and
+        its draw counter advances by the steps it took (``steps_used``).  The standalone loops forever on a greedy policy
+        that never ends an episode; here a run also stops after ``max_steps`` steps (default ``1000 * episodes``) with
+        ``finished[r]`` False."""
+        self._check_env(env)
+        episodes = int(episodes)
+        if episodes < 0:
+            msg = "episodes must be >= 0"
+            raise ValueError(msg)
+        max_steps = 1000 * episodes if max_steps is None else int(max_steps)
+        if max_steps < 0:
+            msg = "max_steps must be >= 0"
+            raise ValueError(msg)
+        if episodes == 0:  # the standalone's loop does not run: no step, no draw
+            env.bind(self)
+            env.reset_device(seed=42)
+            M = self.runs
+            zeros = np.zeros(M, dtype=np.int64)
+            return PopulationEval(np.zeros(M, dtype=np.float32), zeros, np.empty(0, dtype=np.float32),
+                                  np.zeros(M + 1, dtype=np.int64), zeros.copy(), np.ones(M, dtype=bool))
+        return self._evaluate(env, max_steps, episodes, log)
+
+    def _evaluate(self, env, steps, episodes, log) -> PopulationEval:
+        env.bind(self)
+        env.reset_device(seed=42)
+        M = self.runs
+        counts = np.empty(M, dtype=np.int64)
+        sums = np.empty(M, dtype=np.float32)
+        used = np.empty(M, dtype=np.int64)
+        status = np.empty(M, dtype=np.uint32)
+        st = _lib.RolloutStats()
+        total = self._lib.qe_population_evaluate(
+            self._h, env.handle, steps, episodes, 1 if log else 0, C.byref(st), _lib.ptr(counts, C.c_int64),
+            _lib.ptr(sums, C.c_float), _lib.ptr(used, C.c_int64), _lib.ptr(status, C.c_uint32))
+        empty = total == _lib.ERR_INDEX
+        if total < 0 and not empty:
+            _lib.check(total)
+        self.last_stats = {f: getattr(st, f) for f, _ in st._fields_}
+        total = int(counts.sum())
+        rets = np.empty(total if log else 0, dtype=np.float32)
+        if log and total:
+            _lib.check(self._lib.qe_population_log(self._h, total, None, _lib.ptr(rets, C.c_float)))
+        offsets = np.zeros(M + 1, dtype=np.int64)
+        if log:
+            np.cumsum(counts, out=offsets[1:])
+        result = PopulationEval(sums, counts, rets, offsets, used, (status & 2) == 0)
+        if empty:
+            bad = np.flatnonzero(status & 1).tolist()
+            err = IndexError(f"Cannot choose from an empty sequence (runs {', '.join(map(str, bad))})")
+            err.runs = bad
+            err.result = result
+            raise err
+        return result
+
+    def train(self, env, steps, val_env, val_every_n_steps, val_steps=None, val_episodes=None, curr_state_dict=None,
+              max_val_steps=None) -> PopulationTraining:
+        """The standalone ``train`` (base_runtime.BaseRuntime.train) for every run at once: segments of
+        ``val_every_n_steps`` training steps (the last one shorter if it does not divide ``steps``), each followed by a
+        greedy evaluation on ``val_env`` -- ``val_steps`` steps or ``val_episodes`` episodes (bounded by
+        ``max_val_steps``, see :meth:`evaluate_episodes`).  As in the reference, every segment starts from the
+        ``curr_state_dict`` passed in (None: the training environment is reset before each segment)."""
+        if (val_steps is None) == (val_episodes is None):
+            msg = "Exactly one of val_steps or val_episodes must be specified."
+            raise ValueError(msg)
+        self._check_env(env)
+        self._check_env(val_env)
+        segments, val_totals, val_finished = [], [], []
+        state_dict = None
+        for step in range(0, int(steps), int(val_every_n_steps)):
+            res = self.run_steps(min(val_every_n_steps, steps - step), env, curr_state_dict)
+            segments.append(res)
+            state_dict = res.state_dict
+            if val_steps is not None:
+                ev = self.evaluate_steps(val_env, val_steps)
+            else:
+                ev = self.evaluate_episodes(val_env, val_episodes, max_val_steps)
+            val_totals.append(ev.totals)
+            val_finished.append(ev.finished)
+        M = self.runs
+        counts = np.zeros(M, dtype=np.int64)
+        for res in segments:
+            counts += res.episode_counts
+        offsets = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        returns = np.empty(int(offsets[-1]), dtype=np.float32)
+        at = offsets[:-1].copy()  # next free slot of each run
+        for res in segments:  # each segment's returns after the run's earlier ones
+            run_of = np.repeat(np.arange(M), res.episode_counts)
+            returns[at[run_of] + np.arange(run_of.size) - res.offsets[run_of]] = res.returns
+            at += res.episode_counts
+        shape = (len(segments), M)
+        return PopulationTraining(returns, offsets, np.array(val_totals, dtype=np.float32).reshape(shape),
+                                  np.array(val_finished, dtype=bool).reshape(shape), segments, state_dict)
+
+
+__all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
+           "schedule_descriptor"]

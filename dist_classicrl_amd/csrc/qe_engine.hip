@@ -875,7 +875,11 @@ int qe_table_cells(qe_engine* e, const int32_t* states, const int32_t* actions, 
 void* qe_table_dev(qe_engine* e) { return e->q; }
 int64_t qe_table_row_stride(qe_engine* e) { return e->ld; }
 
-int qe_set_step_counter(qe_engine* e, uint64_t step) { e->step_ctr = step; return QE_OK; }
+int qe_set_step_counter(qe_engine* e, uint64_t step) {
+    e->step_ctr = step;
+    e->pop.off_any = false;  // a population: every run continues from `step`
+    return QE_OK;
+}
 uint64_t qe_get_step_counter(qe_engine* e) { return e->step_ctr; }
 int qe_set_agent_offset(qe_engine* e, uint32_t off) { e->agent_offset = off; return QE_OK; }
 

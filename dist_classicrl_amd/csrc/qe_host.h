@@ -166,11 +166,20 @@ struct PopState {
     PinnedBuf<float> h_ret;
     std::vector<int32_t> log_step;     // episode log of the latest call in (run, episode) order
     std::vector<float> log_ret;
+    // Per-run draw counters: run r's next step is qe_engine::step_ctr + step_off[r].  step_off is only read while
+    // off_any (some offset is non-zero: an episode-based evaluation ended the runs after different step counts).
+    DevBuf<unsigned long long> step_off;
+    bool off_any = false;
+    DevBuf<long long> used;            // greedy evaluation, episode mode: steps each run took in the call ...
+    DevBuf<uint8_t> done;              // ... and whether it has reached its episode count
+    PinnedBuf<uint8_t> h_done;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
         seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
         h_cnt.release(); h_step.release(); h_ret.release();
+        step_off.release(); used.release(); done.release(); h_done.release();
+        off_any = false;
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         ev0 = ev1 = nullptr;
@@ -383,12 +392,14 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   persistent path only: bits 4-5 LEAN (0 generic, 1 plain training rollout, 2 + delta log), bit 6 HELP (draw-producing
 //   wavefronts), bit 7 FULL (every lane an agent), bit 8 SEQ (built without the general ordered path), bit 9 the
 //   512-agent build, bit 10 the dataflow kernel (k_rollout_df), bits 12-19 NV (16-byte loads per fp32 row), bit 20
-//   masked environment; path 6 = population (k_rollout_runs) with the same NV and masked bits
+//   masked environment; path 6 = population (k_rollout_runs) and path 7 = population greedy evaluation
+//   (k_evaluate_runs), both with the same NV and masked bits
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
                   QE_VARIANT_EVAL = (int64_t)RolloutPath::Eval;
 constexpr int64_t QE_VARIANT_RUNS = 6;  // population path (k_rollout_runs): bits 12-19 NV, bit 20 masked, as persistent
+constexpr int64_t QE_VARIANT_RUNS_EVAL = 7;  // population greedy evaluation (k_evaluate_runs): the same NV and masked bits
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -400,6 +411,10 @@ int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev
 // population path: one launch of `steps` steps of every run (qe_inst_runs.hip); returns its kernel_variant
 template <typename T, class Env>
 int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps);
+// ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
+template <typename T, class Env>
+int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
+                             long long episodes, long long* used, uint8_t* done);
 // resident workgroups per CU of the k_step_turn build this engine would launch (occupancy query), 0 on failure
 template <typename T, class Env>
 int turn_occupancy(const qe_engine* e);

@@ -1,6 +1,7 @@
 // qe_population.hip -- host side of the population path (include/qlearn_engine.h, "population"): M independent
-// single-agent runs in one [M * S, ld] table, stepped by k_rollout_runs (qe_rollout_runs.h, instantiated in
-// qe_inst_runs.hip), plus the compaction of the per-run episode-log segments.
+// single-agent runs in one [M * S, ld] table, trained by k_rollout_runs and evaluated greedily by k_evaluate_runs
+// (qe_rollout_runs.h, instantiated in qe_inst_runs.hip), plus the compaction of the per-run episode-log segments and
+// the per-run draw counters.
 #include "qe_host.h"
 
 namespace {
@@ -64,6 +65,117 @@ int64_t by_env(int kind, F f) {
 int need_population(const qe_engine* e) {
     if (!e) return qe_fail(QE_ERR_INVALID, "engine is NULL");
     if (!e->pop.runs) return qe_fail(QE_ERR_INVALID, "not a population engine (qe_create_population)");
+    return QE_OK;
+}
+
+// Steps per launch of a call of `steps` steps of M runs (the budgets above).
+long long launch_len(int64_t M, int64_t steps, bool log) {
+    long long per_launch = std::max<long long>(1, RUNS_STEP_BUDGET / M);
+    if (log) per_launch = std::min<long long>(per_launch, std::max<long long>(1, RUNS_LOG_BUDGET / M));
+    if (steps > 0) per_launch = std::min<long long>(per_launch, steps);
+    return per_launch;
+}
+
+int log_reserve(PopState& P, size_t m, long long per_launch) {
+    const size_t seg = m * (size_t)per_launch;
+    HIP_TRY(P.seg_cnt.ensure(m)); HIP_TRY(P.off.ensure(m + 1)); HIP_TRY(P.seg_step.ensure(seg)); HIP_TRY(P.seg_ret.ensure(seg));
+    HIP_TRY(P.out_step.ensure(seg)); HIP_TRY(P.out_ret.ensure(seg)); HIP_TRY(P.h_cnt.ensure(m + 1));
+    return QE_OK;
+}
+
+// Episode log of a call, launch-major: per launch, each run's entries in order.
+struct CallLog {
+    std::vector<int32_t> cnt, step;
+    std::vector<float> ret;
+};
+
+// Compacts the segments the launch of `k` steps has just written and appends them to `L` (synchronises the stream).
+int log_launch(qe_engine* e, long long k, CallLog& L, int64_t& launches) {
+    PopState& P = e->pop;
+    const int64_t M = P.runs;
+    const size_t m = (size_t)M;
+    hipLaunchKernelGGL(k_runs_log_scan, dim3(1), dim3(1024), 0, e->stream, (const int32_t*)P.seg_cnt.p, M, P.off.p);
+    hipLaunchKernelGGL(k_runs_log_pack, dim3(grid_for(M, 256)), dim3(256), 0, e->stream, (const int32_t*)P.seg_cnt.p,
+                       (const int32_t*)P.off.p, (const int32_t*)P.seg_step.p, (const float*)P.seg_ret.p, k, M,
+                       P.out_step.p, P.out_ret.p);
+    launches += 2;
+    HIP_TRY(hipMemcpyAsync(P.h_cnt.p, P.seg_cnt.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.h_cnt.p + m, P.off.p + m, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t total = (size_t)P.h_cnt.p[m];
+    L.cnt.insert(L.cnt.end(), P.h_cnt.p, P.h_cnt.p + m);
+    if (total) {
+        HIP_TRY(P.h_step.ensure(total)); HIP_TRY(P.h_ret.ensure(total));
+        HIP_TRY(hipMemcpyAsync(P.h_step.p, P.out_step.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(P.h_ret.p, P.out_ret.p, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        L.step.insert(L.step.end(), P.h_step.p, P.h_step.p + total);
+        L.ret.insert(L.ret.end(), P.h_ret.p, P.h_ret.p + total);
+    }
+    return QE_OK;
+}
+
+// Launch-major -> (run, episode) order, into P.log_step / P.log_ret (qe_population_log).
+void log_finish(PopState& P, const CallLog& L, const std::vector<long long>& counts) {
+    const size_t m = (size_t)P.runs;
+    std::vector<size_t> at(m + 1, 0);
+    for (size_t r = 0; r < m; ++r) at[r + 1] = at[r] + (size_t)counts[r];
+    P.log_step.resize(L.step.size());
+    P.log_ret.resize(L.ret.size());
+    size_t src = 0;
+    for (size_t l = 0; l < L.cnt.size() / std::max<size_t>(m, 1); ++l)
+        for (size_t r = 0; r < m; ++r)
+            for (int32_t j = 0; j < L.cnt[l * m + r]; ++j, ++src) {
+                P.log_step[at[r]] = L.step[src];
+                P.log_ret[at[r]] = L.ret[src];
+                ++at[r];
+            }
+}
+
+// QE_ERR_INDEX naming the (first eight) runs with bit 0 of their status set, else QE_OK.
+int fail_empty(const std::vector<uint32_t>& st) {
+    for (size_t r = 0; r < st.size(); ++r)
+        if (st[r] & 1u) {
+            std::string runs;
+            int named = 0;
+            for (size_t q = r; q < st.size() && named < 8; ++q)
+                if (st[q] & 1u) { runs += (named++ ? ", " : "") + std::to_string(q); }
+            return qe_fail(QE_ERR_INDEX, "Cannot choose from an empty sequence (runs %s%s)", runs.c_str(), named == 8 ? ", ..." : "");
+        }
+    return QE_OK;
+}
+
+// Every run's draw counter: step_ctr + its offset.
+int get_counters(qe_engine* e, uint64_t* out) {
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    std::vector<unsigned long long> off(m, 0ull);
+    if (P.off_any) {
+        HIP_TRY(hipMemcpyAsync(off.data(), P.step_off.p, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    for (size_t r = 0; r < m; ++r) out[r] = e->step_ctr + off[r];
+    return QE_OK;
+}
+
+// Run r's counter := in[r]: step_ctr = in[0] and offsets relative to it (uint64 arithmetic wraps both ways); the kernels
+// read the offsets only if one of them is non-zero.
+int set_counters(qe_engine* e, const uint64_t* in) {
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    std::vector<unsigned long long> off(m);
+    bool any = false;
+    for (size_t r = 0; r < m; ++r) {
+        off[r] = (unsigned long long)(in[r] - in[0]);
+        any |= off[r] != 0;
+    }
+    if (any) {
+        HIP_TRY(P.step_off.ensure(m));
+        HIP_TRY(hipMemcpyAsync(P.step_off.p, off.data(), m * sizeof(unsigned long long), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    e->step_ctr = in[0];
+    P.off_any = any;
     return QE_OK;
 }
 
@@ -155,14 +267,9 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
     HIP_TRY(hipSetDevice(e->device));
     const int64_t M = P.runs;
     const size_t m = (size_t)M;
-    long long per_launch = std::max<long long>(1, RUNS_STEP_BUDGET / M);
-    if (log) per_launch = std::min<long long>(per_launch, std::max<long long>(1, RUNS_LOG_BUDGET / M));
-    if (steps > 0) per_launch = std::min<long long>(per_launch, steps);
-    if (log) {
-        const size_t seg = m * (size_t)per_launch;
-        HIP_TRY(P.seg_cnt.ensure(m)); HIP_TRY(P.off.ensure(m + 1)); HIP_TRY(P.seg_step.ensure(seg)); HIP_TRY(P.seg_ret.ensure(seg));
-        HIP_TRY(P.out_step.ensure(seg)); HIP_TRY(P.out_ret.ensure(seg)); HIP_TRY(P.h_cnt.ensure(m + 1));
-    }
+    const long long per_launch = launch_len(M, steps, log != 0);
+    if (log)
+        if (int rc = log_reserve(P, m, per_launch)) return rc;
     env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
     HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
     HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
@@ -172,9 +279,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
     const bool masked = env->p.masked != 0 || env->p.kind == QE_ENV_TICTACTOE;
     const int nan_select = masked && e->A > 10 ? 1 : 0;
     const EnvCtx ev = make_envctx(e, env);
-    // launch-major log of the call: per launch, each run's entries in order
-    std::vector<int32_t> cnt_all, step_all;
-    std::vector<float> ret_all;
+    CallLog L;
     int64_t launches = 0, variant = QE_VARIANT_RUNS;
     HIP_TRY(hipEventRecord(P.ev0, e->stream));
     for (long long t = 0; t < steps; t += per_launch) {
@@ -192,6 +297,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.seed_lo = (uint32_t)e->seed; c.seed_hi = (uint32_t)(e->seed >> 32);
                 c.mode = mode; c.nan_select = nan_select;
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
+                c.step_off = P.off_any ? P.step_off.p : nullptr;
                 return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
             };
             return e->dtype == QE_F32 ? go(float{}) : go(double{});
@@ -200,26 +306,8 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
         variant = v;
         ++launches;
         HIP_TRY(hipGetLastError());
-        if (log) {
-            hipLaunchKernelGGL(k_runs_log_scan, dim3(1), dim3(1024), 0, e->stream, (const int32_t*)P.seg_cnt.p, M, P.off.p);
-            hipLaunchKernelGGL(k_runs_log_pack, dim3(grid_for(M, 256)), dim3(256), 0, e->stream, (const int32_t*)P.seg_cnt.p,
-                               (const int32_t*)P.off.p, (const int32_t*)P.seg_step.p, (const float*)P.seg_ret.p, (long long)k, M,
-                               P.out_step.p, P.out_ret.p);
-            launches += 2;
-            HIP_TRY(hipMemcpyAsync(P.h_cnt.p, P.seg_cnt.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipMemcpyAsync(P.h_cnt.p + m, P.off.p + m, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            const size_t total = (size_t)P.h_cnt.p[m];
-            cnt_all.insert(cnt_all.end(), P.h_cnt.p, P.h_cnt.p + m);
-            if (total) {
-                HIP_TRY(P.h_step.ensure(total)); HIP_TRY(P.h_ret.ensure(total));
-                HIP_TRY(hipMemcpyAsync(P.h_step.p, P.out_step.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(hipMemcpyAsync(P.h_ret.p, P.out_ret.p, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                step_all.insert(step_all.end(), P.h_step.p, P.h_step.p + total);
-                ret_all.insert(ret_all.end(), P.h_ret.p, P.h_ret.p + total);
-            }
-        }
+        if (log)
+            if (int rc = log_launch(e, k, L, launches)) return rc;
     }
     HIP_TRY(hipEventRecord(P.ev1, e->stream));
     e->step_ctr += (uint64_t)steps;
@@ -239,20 +327,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
         total += counts[r];
     }
     if (status) memcpy(status, st.data(), m * sizeof(uint32_t));
-    if (log) {  // launch-major -> (run, episode) order
-        std::vector<size_t> at(m + 1, 0);
-        for (size_t r = 0; r < m; ++r) at[r + 1] = at[r] + (size_t)counts[r];
-        P.log_step.resize(step_all.size());
-        P.log_ret.resize(ret_all.size());
-        size_t src = 0;
-        for (size_t l = 0; l < cnt_all.size() / std::max<size_t>(m, 1); ++l)
-            for (size_t r = 0; r < m; ++r)
-                for (int32_t j = 0; j < cnt_all[l * m + r]; ++j, ++src) {
-                    P.log_step[at[r]] = step_all[src];
-                    P.log_ret[at[r]] = ret_all[src];
-                    ++at[r];
-                }
-    }
+    if (log) log_finish(P, L, counts);
     if (stats) {
         float ms = 0.0f;
         if (steps > 0) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
@@ -260,15 +335,130 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
         stats->dominant_ms = ms; stats->dominant_launches = launches; stats->dominant_env_steps = steps * M;
         stats->kernel_variant = variant;
     }
-    for (size_t r = 0; r < m; ++r)
-        if (st[r]) {
-            std::string runs;
-            int named = 0;
-            for (size_t q = r; q < m && named < 8; ++q)
-                if (st[q]) { runs += (named++ ? ", " : "") + std::to_string(q); }
-            return qe_fail(QE_ERR_INDEX, "Cannot choose from an empty sequence (runs %s%s)", runs.c_str(), named == 8 ? ", ..." : "");
-        }
+    if (int rc = fail_empty(st)) return rc;
     return total;
+}
+
+int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t episodes, int32_t log, qe_rollout_stats* stats,
+                               int64_t* ep_count, float* ep_sum, int64_t* used, uint32_t* status) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    P.log_step.clear();
+    P.log_ret.clear();
+    if (!env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
+    if (steps < 0) return qe_fail(QE_ERR_INVALID, "steps must be >= 0");
+    if (episodes < 0) return qe_fail(QE_ERR_INVALID, "episodes must be >= 0");
+    if (e->ld > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions");
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t M = P.runs;
+    const size_t m = (size_t)M;
+    const long long per_launch = launch_len(M, steps, log != 0);
+    if (log)
+        if (int rc = log_reserve(P, m, per_launch)) return rc;
+    if (episodes) {
+        HIP_TRY(P.used.ensure(m)); HIP_TRY(P.done.ensure(m)); HIP_TRY(P.h_done.ensure(m));
+        HIP_TRY(hipMemsetAsync(P.used.p, 0, m * sizeof(long long), e->stream));
+        HIP_TRY(hipMemsetAsync(P.done.p, 0, m, e->stream));
+    }
+    env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
+    HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_sum.p, 0, m * sizeof(float), e->stream));
+    // The standalone evaluation's rule (rollout_ctx): deterministic selection takes the list variants, which step over a
+    // NaN, for rows of at most 10 actions (q_learning_optimal.py:673), masked or not
+    const int nan_select = e->A > 10 ? 1 : 0;
+    const EnvCtx ev = make_envctx(e, env);
+    CallLog L;
+    int64_t launches = 0, variant = QE_VARIANT_RUNS_EVAL;
+    bool all_done = false;
+    HIP_TRY(hipEventRecord(P.ev0, e->stream));
+    for (long long t = 0; t < steps && !all_done; t += per_launch) {
+        const long long k = std::min<long long>(per_launch, steps - t);
+        const int64_t v = by_env(env->p.kind, [&](auto tag) -> int64_t {
+            using Env = decltype(tag);
+            auto go = [&](auto tt) -> int64_t {
+                using T = decltype(tt);
+                RunsCtx<T> c{};
+                c.q = (T*)e->q; c.S = P.S; c.M = M;
+                c.obs = env->n.p; c.aux = env->aux.p; c.acc = env->acc.p;
+                c.status = P.status.p; c.ep_count = P.ep_count.p; c.ep_sum = P.ep_sum.p;
+                if (log) { c.seg_cnt = P.seg_cnt.p; c.seg_step = P.seg_step.p; c.seg_ret = P.seg_ret.p; c.seg_len = k; }
+                c.seed_lo = (uint32_t)e->seed; c.seed_hi = (uint32_t)(e->seed >> 32);
+                c.nan_select = nan_select;
+                c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
+                c.step_off = P.off_any ? P.step_off.p : nullptr;
+                return launch_evaluate_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, episodes,
+                                                    episodes ? P.used.p : nullptr, episodes ? P.done.p : nullptr);
+            };
+            return e->dtype == QE_F32 ? go(float{}) : go(double{});
+        });
+        if (v < 0) return qe_fail(QE_ERR_INVALID, "unknown env kind %d", (int)env->p.kind);
+        variant = v;
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (log)
+            if (int rc = log_launch(e, k, L, launches)) return rc;
+        if (episodes) {  // no further launch once every run has its episodes
+            HIP_TRY(hipMemcpyAsync(P.h_done.p, P.done.p, m, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            all_done = std::all_of(P.h_done.p, P.h_done.p + m, [](uint8_t d) { return d != 0; });
+        }
+    }
+    HIP_TRY(hipEventRecord(P.ev1, e->stream));
+    std::vector<long long> counts(m), took(m, steps);
+    std::vector<uint32_t> st(m);
+    HIP_TRY(hipMemcpyAsync(counts.data(), P.ep_count.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), P.status.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (ep_sum) HIP_TRY(hipMemcpyAsync(ep_sum, P.ep_sum.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (episodes) {
+        HIP_TRY(hipMemcpyAsync(took.data(), P.used.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(P.h_done.p, P.done.p, m, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    // every run's draw counter moves on by the steps it took (the standalone evaluate_episodes: start + used)
+    if (episodes) {
+        std::vector<uint64_t> ctr(m);
+        if (int rc = get_counters(e, ctr.data())) return rc;
+        for (size_t r = 0; r < m; ++r) ctr[r] += (uint64_t)took[r];
+        if (int rc = set_counters(e, ctr.data())) return rc;
+    } else {
+        e->step_ctr += (uint64_t)steps;
+    }
+    long long total = 0, env_steps = 0;
+    for (size_t r = 0; r < m; ++r) {
+        if (episodes && !P.h_done.p[r]) st[r] |= 2u;  // stopped by the bound `steps`
+        if (ep_count) ep_count[r] = counts[r];
+        if (used) used[r] = took[r];
+        total += counts[r];
+        env_steps += took[r];
+    }
+    if (status) memcpy(status, st.data(), m * sizeof(uint32_t));
+    if (log) log_finish(P, L, counts);
+    if (stats) {
+        float ms = 0.0f;
+        if (launches) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
+        stats->kernel_ms = ms; stats->launches = launches; stats->episodes = total;
+        stats->dominant_ms = ms; stats->dominant_launches = launches; stats->dominant_env_steps = env_steps;
+        stats->kernel_variant = variant;
+    }
+    if (int rc = fail_empty(st)) return rc;
+    return total;
+}
+
+int qe_population_step_counters(qe_engine* e, uint64_t* out) {
+    if (int rc = need_population(e)) return rc;
+    if (!out) return qe_fail(QE_ERR_INVALID, "out is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    return get_counters(e, out);
+}
+
+int qe_population_set_step_counters(qe_engine* e, const uint64_t* in) {
+    if (int rc = need_population(e)) return rc;
+    if (!in) return qe_fail(QE_ERR_INVALID, "in is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    return set_counters(e, in);
 }
 
 int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret) {

@@ -8,7 +8,7 @@
 //
 // Run r after K steps is bit for bit the standalone one-agent rollout (k_rollout_lane with N = 1) on a one-agent
 // environment with agent offset agent_offset + r: one step is
-//   1. draws of (agent_offset + r, step);
+//   1. draws of (agent_offset + r, step), step = the launch's step0 + the run's own offset (step_off) + t;
 //   2. epsilon-greedy pick (select_lane) from the row of the current state, held in registers;
 //   3. Env::step;
 //   4. gather of the next state's row: the TD maximum (np.max over its valid columns) and the next pick;
@@ -67,6 +67,7 @@ struct RunsCtx {
     int mode, nan_select;
     unsigned long long step0;  // draw-protocol step of this launch's first step
     long long t_call;          // its index within the call (log entries)
+    const unsigned long long* step_off;  // [M] per-run offsets added to step0 (NULL: every run draws at step0 + t)
 };
 
 template <typename T, class Env, int NV, bool MASKED>
@@ -88,13 +89,14 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_rollout_runs(RunsCtx<T> c, EnvCt
     bool empty = false;
     const bool nan_sel = c.nan_select != 0;
     const uint32_t id = ev.agent_offset + (uint32_t)r;  // the draw key of every rollout: the environment's agent id
+    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
 
     RowV<T, NV> row;
     load_row_lane<NV>(row, q, n);
     M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = c.step0 + (unsigned long long)t;
+        const unsigned long long step = step0 + (unsigned long long)t;
         const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
         const bool explore = (unsigned long long)x.x < eps_threshold(eps_v);
         T picked;
@@ -143,6 +145,84 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_rollout_runs(RunsCtx<T> c, EnvCt
     c.ep_sum[r] = sum;
     if (c.seg_len) c.seg_cnt[r] = logged;
     if (empty) c.status[r] = 1u;
+}
+
+// Greedy evaluation of every run (qe_population_evaluate): run r is the standalone one-agent evaluate_steps /
+// evaluate_episodes (k_eval with N = 1).  One step is the draws of (agent_offset + r, step), the pick at epsilon 0
+// (select_lane with explore = false: the reference's deterministic=True, ties still broken by the draws), Env::step and
+// the gather of the next row -- no table store, no TD target, no schedule.  Same launch shape, per-run state and log
+// segments as k_rollout_runs; c.eps / c.lr / c.gamma are not read.
+//   episodes == 0  step mode: every run takes `steps` steps.
+//   episodes > 0   a run stops at the end of the step in which its episode count of the call reaches `episodes`:
+//                  done[r] is set and later launches skip the run.  used[r] accumulates the steps it took.
+template <typename T, class Env, int NV, bool MASKED>
+__global__ __launch_bounds__(RUNS_BLOCK) void k_evaluate_runs(RunsCtx<T> c, EnvCtx ev, long long steps, long long episodes,
+                                                              long long* used, uint8_t* done) {
+    using M = typename LaneMask<NV>::type;
+    const int64_t r = (int64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
+    if (r >= c.M) return;
+    if (episodes && done[r]) {  // finished in an earlier launch: an empty log segment, nothing else
+        if (c.seg_len) c.seg_cnt[r] = 0;
+        return;
+    }
+    const T* const q = c.q + r * c.S * (4 * NV);
+    int32_t n = c.obs[r];
+    uint32_t aux = c.aux[r];
+    float acc = c.acc[r];
+    long long count = c.ep_count[r];
+    float sum = c.ep_sum[r];
+    int32_t logged = 0;
+    bool empty = false, finished = false;
+    const bool nan_sel = c.nan_select != 0;
+    const uint32_t id = ev.agent_offset + (uint32_t)r;
+    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+
+    RowV<T, NV> row;
+    load_row_lane<NV>(row, q, n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    long long t = 0;
+    while (t < steps) {
+        const unsigned long long step = step0 + (unsigned long long)t;
+        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
+        const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
+        T picked;
+        int act = select_lane<T, NV, M>(rowm, valid, false, x.y, x.z, &picked, nan_sel && row_nan_lane<NV>(rowm));
+        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
+            empty = true;
+            act = 0;
+        }
+        const Transition tr = Env::step(ev, r, n, aux, act, step);
+        n = tr.next_obs;
+        acc += tr.reward;
+        ++t;
+        if (tr.terminated) {
+            if (logged < c.seg_len) {
+                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t - 1);
+                c.seg_ret[r * c.seg_len + logged] = acc;
+                ++logged;
+            }
+            sum += acc;
+            ++count;
+            acc = 0.0f;
+            if (episodes && count >= episodes) {
+                finished = true;
+                break;
+            }
+        }
+        load_row_lane<NV>(row, q, n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    }
+    c.obs[r] = n;
+    c.aux[r] = aux;
+    c.acc[r] = acc;
+    c.ep_count[r] = count;
+    c.ep_sum[r] = sum;
+    if (c.seg_len) c.seg_cnt[r] = logged;
+    if (empty) c.status[r] = 1u;
+    if (episodes) {
+        used[r] += t;
+        if (finished) done[r] = 1;
+    }
 }
 
 }  // namespace qe

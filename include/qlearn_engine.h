@@ -90,7 +90,8 @@ typedef struct qe_rollout_stats {
                                 agent, bit 8 built without the general ordered path ("light"), bit 9 the 512-agent build,
                                 bit 10 the dataflow kernel (sharers of a row ordered by value hand-over in LDS),
                                 bits 12-19 16-byte loads per row, bit 20 masked environment (tests assert on these);
-                                path 6: population (qe_population_rollout), with the same NV and masked bits */
+                                path 6: population (qe_population_rollout), path 7: population greedy evaluation
+                                (qe_population_evaluate), both with the same NV and masked bits */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -151,8 +152,8 @@ void* qe_table_dev(qe_engine* e);       /* device pointer of the table (for RCCL
 int64_t qe_table_row_stride(qe_engine* e); /* ld, in elements */
 
 /* ---- draw counter ---------------------------------------------------------------------------*/
-int qe_set_step_counter(qe_engine* e, uint64_t step);
-uint64_t qe_get_step_counter(qe_engine* e);
+int qe_set_step_counter(qe_engine* e, uint64_t step);  /* population: every run continues from `step` */
+uint64_t qe_get_step_counter(qe_engine* e);            /* population: the counter of run 0 (see qe_population_step_counters) */
 int qe_set_agent_offset(qe_engine* e, uint32_t offset); /* draw-protocol id of local agent 0 */
 
 /* ---- action selection -----------------------------------------------------------------------
@@ -296,8 +297,20 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         had no selectable action: the call returns QE_ERR_INDEX after filling the outputs, the other
  *                         runs are unaffected).  `log` != 0 keeps the episode log of the call (qe_population_log).
  *                         Returns the number of episodes that ended, or a negative qe_status.
+ *   qe_population_evaluate  greedy evaluation of every run: run r is the standalone one-agent evaluate_steps (episodes
+ *                         == 0: `steps` steps) or evaluate_episodes (episodes > 0: the run stops at the end of the step in
+ *                         which its episode count reaches `episodes`, or after `steps` steps, whichever comes first; no
+ *                         launch follows once every run has stopped).  Tables and schedules are untouched; the
+ *                         environment state moves on.  Per-run outputs, each `runs` entries, any may be NULL: episodes
+ *                         ended, float32 sequential sum of their returns, steps taken, status (bit 0: some step had no
+ *                         selectable action -- QE_ERR_INDEX after filling the outputs; bit 1: episode mode stopped by
+ *                         the bound `steps`, not an error).  `log` as for qe_population_rollout.  Returns the number of
+ *                         episodes that ended, or a negative qe_status.
  *   qe_population_log     the latest call's episode log in (run, episode) order: step within the call and return of
- *                         the first `cap` entries; returns the count. */
+ *                         the first `cap` entries; returns the count.
+ *   qe_population_step_counters / qe_population_set_step_counters  every run's draw counter (`runs` entries).  Each
+ *                         call of the rollout or of a step-mode evaluation advances every run by `steps`; an
+ *                         episode-mode evaluation advances run r by the steps it took, so the counters may differ. */
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
 typedef struct qe_run_schedule {
     double value;      /* the value read at the next step */
@@ -314,7 +327,11 @@ int qe_population_schedules(qe_engine* e, double* eps_values, double* lr_values)
 int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t mode, int32_t log, qe_rollout_stats* stats,
                               int64_t* ep_count, float* ep_sum, int32_t* obs, uint32_t* aux, float* agent_rewards,
                               uint32_t* status);
+int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t episodes, int32_t log,
+                               qe_rollout_stats* stats, int64_t* ep_count, float* ep_sum, int64_t* used, uint32_t* status);
 int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret);
+int qe_population_step_counters(qe_engine* e, uint64_t* out);
+int qe_population_set_step_counters(qe_engine* e, const uint64_t* in);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

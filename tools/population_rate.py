@@ -1,13 +1,17 @@
 """Aggregate env-steps/s of the population path (QLearningPopulation, k_rollout_runs) against the standalone one-agent
 rollout on the same environment, measured in the same process.
 
-    python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick]
+    python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
 M = 4096.  Rate = M x steps / wall time of one timed call (after a warm-up call; the call returns after the device has
 finished).  Writes DIR/population_rate.json and prints one line per workload.  For kernel time and bytes per env-step,
 run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/population_rate.py --out DIR --quick`.
+
+--evaluate measures greedy evaluation instead (QLearningPopulation.evaluate_steps, k_evaluate_runs) on the same
+workloads and M values, against the standalone one-agent evaluate_steps, after 200 training steps, and writes
+DIR/population_eval_rate.json.
 """
 
 from __future__ import annotations
@@ -72,6 +76,34 @@ def population_rate(make_env, M, S, A, steps, dtype, log):
             "episodes": int(res.episode_counts.sum()), "kernel_variant": int(pop.last_stats["kernel_variant"])}
 
 
+def population_eval_rate(make_env, M, S, A, steps, dtype, log):
+    lr, eps = schedules()
+    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype)
+    pop.run_steps(200, make_env(M), log=False)  # tables that are not all zero
+    env = make_env(M)
+    pop.evaluate_steps(env, min(200, steps), log=log)  # warm-up: code objects, allocations
+    t0 = time.perf_counter()
+    res = pop.evaluate_steps(env, steps, log=log)
+    wall = time.perf_counter() - t0
+    return {"runs": M, "steps": steps, "wall_s": wall, "env_steps_per_s": M * steps / wall,
+            "kernel_ms": pop.last_stats["kernel_ms"], "launches": int(pop.last_stats["launches"]),
+            "episodes": int(res.episode_counts.sum()), "kernel_variant": int(pop.last_stats["kernel_variant"])}
+
+
+def standalone_eval_rate(make_env, S, A, steps, dtype):
+    lr, eps = schedules()
+    algo = OptimalQLearningBase(S, A, 0.99, seed=1, dtype=dtype)
+    rt = GpuRolloutQLearning(algo, lr, eps)
+    rt.history_type = "array"
+    rt.run_steps(200, make_env(1))
+    env = make_env(1)
+    rt.evaluate_steps(env, min(200, steps))
+    t0 = time.perf_counter()
+    rt.evaluate_steps(env, steps)
+    wall = time.perf_counter() - t0
+    return {"steps": steps, "wall_s": wall, "env_steps_per_s": steps / wall}
+
+
 def standalone_rate(make_env, S, A, steps, dtype):
     lr, eps = schedules()
     algo = OptimalQLearningBase(S, A, 0.99, seed=1, dtype=dtype)
@@ -91,6 +123,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10000)
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--quick", action="store_true", help="fewer steps and shapes (profiling runs)")
+    ap.add_argument("--evaluate", action="store_true", help="greedy evaluation (evaluate_steps) instead of training")
     args = ap.parse_args()
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
@@ -112,17 +145,18 @@ def main() -> None:
     lines = []
     for name, make_env, S, A, M, k, log in plan:
         if name not in base_cache:
-            base_cache[name] = standalone_rate(make_env, S, A, min(k, 5000), dtype)
-        pop = population_rate(make_env, M, S, A, k, dtype, log)
+            base_cache[name] = (standalone_eval_rate if args.evaluate else standalone_rate)(make_env, S, A, min(k, 5000), dtype)
+        pop = (population_eval_rate if args.evaluate else population_rate)(make_env, M, S, A, k, dtype, log)
         base = base_cache[name]
-        line = {"workload": name, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
+        line = {"workload": name, "evaluate": args.evaluate, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
                 "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
         lines.append(line)
         print(f"{name:14s} M={M:6d} log={int(log)} {pop['env_steps_per_s'] / 1e6:10.1f} M env-steps/s "
               f"(standalone {base['env_steps_per_s'] / 1e6:.3f} M/s, x{line['speedup_vs_standalone']:.0f}; "
               f"{pop['launches']} launches, kernel {pop['kernel_ms']:.1f} ms)", flush=True)
     args.out.mkdir(parents=True, exist_ok=True)
-    (args.out / "population_rate.json").write_text(json.dumps(lines, indent=1))
+    name = "population_eval_rate.json" if args.evaluate else "population_rate.json"
+    (args.out / name).write_text(json.dumps(lines, indent=1))
 
 
 if __name__ == "__main__":
