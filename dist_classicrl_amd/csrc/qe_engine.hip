@@ -341,7 +341,9 @@ Ctx<T> rollout_ctx(qe_engine* e, qe_env* env, const RolloutSlot& sl, int mode, c
     c.ep_key = sl.ep_key.p; c.ep_ret = sl.ep_ret.p; c.ep_cap = e->ep_cap;
     if (sl.trace_host) c.trace = e->trace.p;
     if (e->dlog && learn) {
-        c.dlog = e->dlog; c.dlog_base = e->dlog_count; c.dlog_cap = e->dlog_cap;
+        // whole steps only (qlearn_engine.h, qe_delta_log_attach): the kernels see a capacity that ends on a step boundary
+        c.dlog = e->dlog; c.dlog_base = e->dlog_count;
+        c.dlog_cap = e->dlog_count + (e->dlog_cap - e->dlog_count) / env->N * env->N;
     }
     c.rp = rp;
     if (sl.path == RolloutPath::Turnstile) {
@@ -423,7 +425,8 @@ int rollout_begin(qe_engine* e, qe_env* env, RolloutSlot& sl, RolloutPath path, 
     }
     if (!sl.fast || sl.timed) HIP_TRY(hipEventRecord(sl.ev1, e->stream));
     HIP_TRY(hipGetLastError());
-    if (e->dlog && learn) e->dlog_count = std::min<long long>(e->dlog_count + steps * env->N, e->dlog_cap);
+    if (e->dlog && learn)  // the steps whose records all fit
+        e->dlog_count += std::min<long long>(steps, (e->dlog_cap - e->dlog_count) / env->N) * env->N;
     e->step_ctr += (uint64_t)steps;
     sl.busy = true;
     return QE_OK;
@@ -739,15 +742,29 @@ int qe_destroy(qe_engine* e) {
     e->b_out.release(); e->b_list.release(); e->b_r.release(); e->b_acc.release(); e->b_term.release();
     e->b_pred.release(); e->b_aux.release(); e->b_mask.release(); e->b_bitmap.release();
     e->b_vals.release(); e->b_vinc.release(); e->ep_key.release(); e->ep_ret.release(); e->trace.release();
-    e->ds_a.release(); e->ds_b.release(); e->ds_hist.release();
+    e->ds_a.release(); e->ds_b.release(); e->ds_hist.release(); e->delta_bad.release();
     if (e->stream && e->own_stream) (void)hipStreamDestroy(e->stream);
     delete e;
     return QE_OK;
 }
 
+// Remote records outside the table (skipped and counted by the apply kernels): reported once, where the host has
+// waited for the stream anyway.
+static int delta_bad_check(qe_engine* e) {
+    if (!e->delta_bad_armed) return QE_OK;
+    unsigned n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, e->delta_bad.p, sizeof n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->delta_bad_armed = false;
+    if (n == 0) return QE_OK;
+    HIP_TRY(hipMemsetAsync(e->delta_bad.p, 0, sizeof n, e->stream));
+    return qe_fail(QE_ERR_INDEX, "%u delta records named a cell outside the table (%lld x %lld cells) and were skipped", n,
+                   (long long)e->S, (long long)e->ld);
+}
+
 int qe_synchronize(qe_engine* e) {
     HIP_TRY(hipStreamSynchronize(e->stream));
-    return QE_OK;
+    return delta_bad_check(e);
 }
 
 int qe_set_option(qe_engine* e, int32_t option, int64_t value) {
@@ -806,7 +823,7 @@ static int table_xfer(qe_engine* e, void* host, int host_dtype, bool up) {
         if (hs == 4) for (size_t k = 0; k < cells; ++k) ((float*)host)[k] = (float)((const double*)staged)[k];
         else for (size_t k = 0; k < cells; ++k) ((double*)host)[k] = (double)((const float*)staged)[k];
     }
-    return QE_OK;
+    return up ? QE_OK : delta_bad_check(e);  // (the table has been copied out either way)
 }
 
 // A range of rows, in the table's own dtype, through the engine's page-locked staging area: the streaming
@@ -1413,9 +1430,23 @@ int64_t qe_episode_log(qe_engine* e, int64_t cap, int32_t* step, int32_t* agent,
 }
 
 // ---- multi-GPU replica sync --------------------------------------------------------------------
+// (Records hold the cell as 32 bits; qe_create admits no table of 2^32 cells or more, padded rows included.)
+// The word the apply kernels count skipped records in (delta_bad_check reads it).
+static int delta_bad_arm(qe_engine* e) {
+    if (!e->delta_bad.p) {
+        HIP_TRY(e->delta_bad.ensure(1));
+        HIP_TRY(hipMemsetAsync(e->delta_bad.p, 0, sizeof(unsigned), e->stream));
+    }
+    e->delta_bad_armed = true;
+    return QE_OK;
+}
+
 int qe_delta_log_attach(qe_engine* e, void* dev_buf, int64_t capacity) {
     if (int rc = not_on_population(e, "the delta log")) return rc;
     if (e->dtype != QE_F32 && dev_buf) return qe_fail(QE_ERR_UNSUPPORTED, "delta log needs a float32 table");
+    if (dev_buf) {
+            if (capacity < 0) return qe_fail(QE_ERR_INVALID, "bad argument");
+    }
     e->dlog = (DeltaEntry*)dev_buf;
     e->dlog_cap = dev_buf ? capacity : 0;
     e->dlog_count = 0;
@@ -1426,11 +1457,12 @@ int qe_delta_log_reset(qe_engine* e) { e->dlog_count = 0; return QE_OK; }
 
 int qe_delta_apply_dev(qe_engine* e, const void* dev_entries, int64_t count) {
     if (int rc = not_on_population(e, "qe_delta_apply_dev")) return rc;
-    if (count <= 0) return QE_OK;
     if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
+    if (count <= 0) return QE_OK;
     HIP_TRY(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_delta_apply<float>, dim3(grid_for(count, 256)), dim3(256), 0, e->stream,
-                       (float*)e->q, (const DeltaEntry*)dev_entries, count);
+    if (int rc = delta_bad_arm(e)) return rc;
+    hipLaunchKernelGGL(k_delta_apply<float>, dim3(grid_for(count, 256)), dim3(256), 0, e->stream, (float*)e->q,
+                       (const DeltaEntry*)dev_entries, count, (uint64_t)e->S * (uint64_t)e->ld, e->delta_bad.p);
     HIP_TRY(hipGetLastError());
     return QE_OK;
 }
@@ -1439,23 +1471,26 @@ int qe_delta_apply_skip_dev(qe_engine* e, const void* dev_entries, int64_t count
                             int64_t skip_end) {
     if (int rc = not_on_population(e, "qe_delta_apply_skip_dev")) return rc;
     if (!e || skip_begin < 0 || skip_end < skip_begin || skip_end > count) return qe_fail(QE_ERR_INVALID, "bad argument");
+    if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     const int64_t live = count - (skip_end - skip_begin);
     if (live <= 0) return QE_OK;
-    if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     HIP_TRY(hipSetDevice(e->device));
+    if (int rc = delta_bad_arm(e)) return rc;
     hipLaunchKernelGGL(k_delta_apply_skip<float>, dim3(grid_for(live, 256)), dim3(256), 0, e->stream, (float*)e->q,
-                       (const DeltaEntry*)dev_entries, count, skip_begin, skip_end - skip_begin);
+                       (const DeltaEntry*)dev_entries, count, skip_begin, skip_end - skip_begin,
+                       (uint64_t)e->S * (uint64_t)e->ld, e->delta_bad.p);
     HIP_TRY(hipGetLastError());
     return QE_OK;
 }
 
 int qe_delta_apply_sorted_dev(qe_engine* e, const void* dev_entries, int64_t count) {
     if (int rc = not_on_population(e, "qe_delta_apply_sorted_dev")) return rc;
-    if (count <= 0) return QE_OK;
     if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
+    if (count <= 0) return QE_OK;
     HIP_TRY(hipSetDevice(e->device));
+    if (int rc = delta_bad_arm(e)) return rc;
     hipLaunchKernelGGL(k_delta_apply_sorted<float>, dim3(grid_for(count, 256)), dim3(256), 0, e->stream, (float*)e->q,
-                       (const DeltaEntry*)dev_entries, count);
+                       (const DeltaEntry*)dev_entries, count, (uint64_t)e->S * (uint64_t)e->ld, e->delta_bad.p);
     HIP_TRY(hipGetLastError());
     return QE_OK;
 }
@@ -1465,11 +1500,12 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
     if (int rc = not_on_population(e, "qe_delta_apply_gathered_dev")) return rc;
     if (!e || !gathered_dev || capacity <= 0 || count < 0 || count > capacity || world < 1 || rank < 0 || rank >= world)
         return qe_fail(QE_ERR_INVALID, "bad argument");
+    if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     const int64_t n = (int64_t)(world - 1) * count;
     if (n <= 0) return QE_OK;
     if (n >= ((int64_t)1 << 32)) return qe_fail(QE_ERR_UNSUPPORTED, "more than 2^32 - 1 remote records in one exchange");
-    if (e->dtype != QE_F32) return qe_fail(QE_ERR_UNSUPPORTED, "delta apply needs a float32 table");
     HIP_TRY(hipSetDevice(e->device));
+    if (int rc = delta_bad_arm(e)) return rc;
     const int n_tiles = (int)((n + DSORT_TILE - 1) / DSORT_TILE);
     HIP_TRY(e->ds_a.ensure((size_t)n));
     HIP_TRY(e->ds_b.ensure((size_t)n));
@@ -1495,7 +1531,8 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
                            (const unsigned*)totals, n_tiles, (const unsigned*)flag);
         in = out;
     }
-    hipLaunchKernelGGL(k_delta_apply_sorted<float>, dim3(grid_for(n, 256)), dim3(256), 0, e->stream, (float*)e->q, in, n);
+    hipLaunchKernelGGL(k_delta_apply_sorted<float>, dim3(grid_for(n, 256)), dim3(256), 0, e->stream, (float*)e->q, in, n, cells,
+                       e->delta_bad.p);
     HIP_TRY(hipGetLastError());
     return QE_OK;
 }

@@ -239,6 +239,8 @@ struct qe_engine {
     // delta log (caller-owned buffer)
     DeltaEntry* dlog = nullptr;
     long long dlog_cap = 0, dlog_count = 0;
+    DevBuf<unsigned> delta_bad;     // [0]: records the apply kernels skipped because their cell lies outside the table
+    bool delta_bad_armed = false;   // an apply step ran since the word was last read
     DevBuf<int32_t> trace;
     // replica exchange: ping-pong buffers and digit counts of the radix sort of the remote records (qe_delta_sort.h)
     DevBuf<DeltaEntry> ds_a, ds_b;

@@ -1408,32 +1408,48 @@ __global__ void k_cells(T* q, int ld, const int32_t* s, const int32_t* a, int64_
     if (op == 0) vals[i] = (double)*p; else *p = (T)vals[i];
 }
 
+// Records come from other ranks: one whose cell lies outside the table (`cells` = S * ld) is skipped and counted in
+// `bad[0]`, which the host reads at its next synchronising call (QE_ERR_INDEX).
 template <typename T>
-__global__ void k_delta_apply(T* q, const DeltaEntry* e, int64_t count) {
+__global__ void k_delta_apply(T* q, const DeltaEntry* e, int64_t count, uint64_t cells, unsigned* bad) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) atomicAdd(q + e[i].cell, (T)e[i].delta);
+    if (i >= count) return;
+    if (e[i].cell >= cells) { atomicAdd(bad, 1u); return; }
+    atomicAdd(q + e[i].cell, (T)e[i].delta);
 }
 
 // the all-gathered logs of every rank, minus this rank's own segment [skip_begin, skip_end)
 template <typename T>
-__global__ void k_delta_apply_skip(T* q, const DeltaEntry* e, int64_t count, int64_t skip_begin, int64_t skip_len) {
+__global__ void k_delta_apply_skip(T* q, const DeltaEntry* e, int64_t count, int64_t skip_begin, int64_t skip_len,
+                                   uint64_t cells, unsigned* bad) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count - skip_len) return;
     if (i >= skip_begin) i += skip_len;
+    if (e[i].cell >= cells) { atomicAdd(bad, 1u); return; }
     atomicAdd(q + e[i].cell, (T)e[i].delta);
 }
 
 // Deterministic form: the records arrive stably sorted by cell (the exchange sorts them: rank-major,
 // slot-minor order within a cell); the first record of every run of one cell adds the whole run
 // sequentially, so the float additions into a cell happen in a fixed order.
+// Out-of-range records are skipped and counted.  The radix sort keys on the bits a valid cell can have, so such a
+// record may sit INSIDE the run of the valid cell that shares its low bits: runs are followed across them.
 template <typename T>
-__global__ void k_delta_apply_sorted(T* q, const DeltaEntry* e, int64_t count) {
+__global__ void k_delta_apply_sorted(T* q, const DeltaEntry* e, int64_t count, uint64_t cells, unsigned* bad) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const uint32_t cell = e[i].cell;
-    if (i > 0 && e[i - 1].cell == cell) return;
+    if (cell >= cells) { atomicAdd(bad, 1u); return; }
+    int64_t p = i - 1;
+    while (p >= 0 && e[p].cell >= cells) --p;
+    if (p >= 0 && e[p].cell == cell) return;
     T v = q[cell];
-    for (int64_t j = i; j < count && e[j].cell == cell; ++j) v = v + (T)e[j].delta;
+    for (int64_t j = i; j < count; ++j) {
+        const uint32_t c = e[j].cell;
+        if (c >= cells) continue;
+        if (c != cell) break;
+        v = v + (T)e[j].delta;
+    }
     q[cell] = v;
 }
 

@@ -137,6 +137,22 @@ class DeltaSync:
         if previous is not None:
             self._finish(*previous)
 
+def apply_mode(deterministic) -> str:
+    """How ``attach_engine`` adds the other ranks' records: ``"gathered"`` (sorted inside the engine, bit-reproducible),
+    ``"torch-sort"`` or ``"atomic"`` (float atomics in arrival order).  Booleans, ``numpy.bool_`` and the integers 0 / 1
+    are taken as booleans; anything else but ``"torch-sort"`` is an error rather than a silent fall to the atomics."""
+    import numpy as np
+
+    if isinstance(deterministic, str):
+        if deterministic == "torch-sort":
+            return "torch-sort"
+    elif isinstance(deterministic, (bool, np.bool_)) or (isinstance(deterministic, (int, np.integer))
+                                                         and deterministic in (0, 1)):
+        return "gathered" if deterministic else "atomic"
+    msg = f"deterministic must be True, False or 'torch-sort', got {deterministic!r}"
+    raise ValueError(msg)
+
+
 def attach_engine(algorithm, sync_every: int, num_agents: int, group=None, overlap: bool = True,
                   deterministic: bool = True) -> DeltaSync:
     """Wire a :class:`DeltaSync` to a HIP engine living on the current CUDA device.
@@ -151,6 +167,7 @@ def attach_engine(algorithm, sync_every: int, num_agents: int, group=None, overl
 
     from dist_classicrl_amd import _lib
 
+    mode = apply_mode(deterministic)  # (before anything touches the device)
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device())
     # The engine and the collectives share ONE non-default torch stream, so kernels, all-gathers and
@@ -180,7 +197,7 @@ def attach_engine(algorithm, sync_every: int, num_agents: int, group=None, overl
                                                    int(world), int(rank)))
 
     sync = DeltaSync(capacity, dev, apply_fn, attach_fn, group, overlap, stream, apply_skip_fn,
-                     apply_sorted_fn if deterministic == "torch-sort" else None,
-                     apply_gathered_fn if deterministic is True else None)
+                     apply_sorted_fn if mode == "torch-sort" else None,
+                     apply_gathered_fn if mode == "gathered" else None)
     stream.wait_stream(torch.cuda.current_stream())  # buffer initialisation ran on the current stream
     return sync

@@ -257,7 +257,17 @@ int64_t qe_episode_log(qe_engine* e, int64_t cap, int32_t* step, int32_t* agent,
 
 /* ---- multi-GPU replica sync (replaces the MPI tier, q_learning_async_dist.py:164-357) ---------
  * Each GPU logs (cell, delta) for its own updates into a caller-owned device buffer of
- * capacity entries x 8 bytes {uint32 cell; float delta}; remote logs are applied with atomicAdd. */
+ * capacity entries x 8 bytes {uint32 cell; float delta}; remote logs are applied with atomicAdd.
+ * Slot of a record: (vector steps logged so far) * N + agent, cell = state * row_stride + action.
+ * Capacity rule: WHOLE STEPS ONLY.  A vector step is logged when all N of its records fit below `capacity`; a step
+ * that does not fit -- and every later one -- writes nothing, on every kernel path, and qe_delta_log_count (a multiple
+ * of N) counts only records that were written.  Slots from the count on are never touched.  qe_delta_log_reset
+ * restarts at slot 0; attach(NULL, 0) detaches.
+ * Limits: float32 tables only (attach and the apply entry points answer QE_ERR_UNSUPPORTED otherwise).  A record
+ * holds the cell in 32 bits; qe_create admits no table of 2^32 cells or more (S * row_stride, padded rows included),
+ * so every cell of an engine's table can be named.  The apply kernels skip
+ * records whose cell lies outside the table and count them; the next qe_synchronize or qe_table_download reports
+ * QE_ERR_INDEX once (the valid records have been applied). */
 int qe_delta_log_attach(qe_engine* e, void* dev_buf, int64_t capacity);
 int64_t qe_delta_log_count(qe_engine* e);
 int qe_delta_log_reset(qe_engine* e);

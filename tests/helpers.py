@@ -150,3 +150,66 @@ def golden_nan_trace(g, name, spec, dt, cells, tseed):
     if raised >= 0:
         out.append({"raised": True})
     return out, base
+
+
+def run_oracle_delta_log(env, steps, dt, sched, learn_mode, gamma=0.99, seed=0):
+    """The closed loop on the NumPy oracle plus the content of the engine's delta log: one (cell = s * A + a, float32
+    increment) record per agent and step in (step, agent) order.  ``OracleRuntime._learn`` is wrapped: the records are
+    computed from its arguments by the reference's own arithmetic on a copy of the table -- ``learn_iter``: the
+    ``lr * (target - Q[s, a])`` of ``single_learn`` when agent i is processed, i.e. after agents 0..i-1 of the step have
+    written; ``learn_vec``: the increment array handed to ``np.add.at`` -- and the copy must end equal to the table the
+    oracle itself produced."""
+    algo = OracleQLearning(env.state_size, env.action_size, gamma, seed=seed, dtype=np.dtype(dt))
+    lr_p, eps_p = schedule_params(sched)
+    rt = OracleRuntime(algo, OracleSchedule(*lr_p), OracleSchedule(*eps_p), learn_mode=learn_mode)
+    rt.trace = []
+    A, cells, deltas = env.action_size, [], []
+    inner = rt._learn
+
+    def learn(states, actions, rewards, next_states, terminateds):
+        masked = isinstance(next_states, dict)
+        s = np.asarray(states["observation"] if masked else states)
+        s2 = np.asarray(next_states["observation"] if masked else next_states)
+        masks = next_states["action_mask"] if masked else None
+        lr = rt.lr_schedule.get_value()
+        q = algo.q_table.copy()
+        cells.append(s.astype(np.int64) * A + actions)
+        with np.errstate(all="ignore"):
+            if learn_mode == "iter":  # single_learn, agent by agent
+                inc = np.empty(len(s), dtype=np.float32)
+                for i in range(len(s)):
+                    if terminateds[i]:
+                        nxt = 0
+                    else:
+                        nxt = np.max(q[s2[i]]) if masks is None else np.max(q[s2[i]][np.where(masks[i])])
+                    u = lr * ((rewards[i] + gamma * nxt) - q[s[i], actions[i]])
+                    inc[i] = u
+                    q[s[i], actions[i]] += u
+            else:  # learn_vec
+                rows = q[s2]
+                if masks is not None:
+                    rows = np.where(masks, rows, -np.inf)
+                targets = rewards + gamma * np.max(rows, axis=1) * (1 - terminateds)
+                u = lr * (targets - q[s, actions])
+                inc = u.astype(np.float32)
+                np.add.at(q, (s, actions), u)
+        deltas.append(inc)
+        inner(states, actions, rewards, next_states, terminateds)
+        assert np.array_equal(q, algo.q_table, equal_nan=True), "the records do not add up to the oracle's own update"
+
+    rt._learn = learn
+    states, _ = env.reset()
+    acc = np.zeros(env.num_agents, dtype=np.float32)
+    history = []
+    for _ in range(steps):
+        states, _ = rt.run_single_step(env, states, acc, history)
+    obs = states["observation"] if isinstance(states, dict) else states
+    return {"actions": np.stack([a for a, _, _ in rt.trace]), "cells": np.concatenate(cells).astype(np.uint32),
+            "deltas": np.concatenate(deltas), "q": algo.q_table, "history": np.array(history, dtype=np.float32),
+            "final_obs": np.asarray(obs, dtype=np.int32), "agent_rewards": acc}
+
+
+def shares_a_cell_within_a_step(cells, n):
+    """True if some step's `n` records name one cell more than once (the case is not contention-free)."""
+    by_step = np.sort(np.asarray(cells).reshape(-1, n), axis=1)
+    return bool((by_step[:, 1:] == by_step[:, :-1]).any())

@@ -181,3 +181,18 @@ def test_exchange_every_step_equals_learn_vec_over_all_agents(tmp_path):
         # float32 deltas added in a different order than np.add.at: 1e-6 relative per increment
         assert np.allclose(q, whole.q, rtol=2e-6, atol=1e-7)
     assert np.count_nonzero(whole.q) > 100
+
+
+def test_attach_engine_argument_is_normalised_or_refused():
+    """``attach_engine(deterministic=...)``: truthy values other than ``True`` used to fall through to float atomics in
+    arrival order without a word (the replica is then not reproducible bit for bit)."""
+    from dist_classicrl_amd.distributed.delta_sync import apply_mode
+
+    for value in (True, 1, np.bool_(True), np.int64(1)):
+        assert apply_mode(value) == "gathered", value
+    for value in (False, 0, np.bool_(False)):
+        assert apply_mode(value) == "atomic", value
+    assert apply_mode("torch-sort") == "torch-sort"
+    for value in ("yes", 2, None, "True", 1.0, -1):
+        with pytest.raises(ValueError):
+            apply_mode(value)

@@ -135,6 +135,74 @@ def test_eight_ranks_worth_of_records_at_the_c4_shard_shape():
     buf.free()
 
 
+@pytest.mark.parametrize("entry", ["apply", "skip", "sorted", "gathered"])
+def test_records_outside_the_table_are_skipped_and_reported(entry):
+    """Three records whose cell lies beyond S * ld among valid ones (one of them sharing its low bits with a valid,
+    repeated cell, so the radix sort files it inside that cell's run): the table equals the CPU simulation of the
+    valid records only, and the next synchronising call reports QE_ERR_INDEX -- once."""
+    _lib, Algo, _, _, _ = _product()
+    lib = _lib.load()
+    S, A, world, count, rank = 1000, 8, 2, 600, 0
+    rng = np.random.default_rng(11)
+    algo = Algo(S, A, 0.99, seed=0)
+    ld = int(lib.qe_table_row_stride(algo.handle))
+    q0 = rng.standard_normal((S, A)).astype(np.float32)
+    algo.q_table = q0
+    rec = _records(rng, world, count, count, S * A, hot=0.3)
+    flat = rec[..., 0].astype(np.int64)
+    rec[..., 0] = (flat // A * ld + flat % A).astype(np.uint32)
+    other = 1 - rank
+    hot_cell = np.bincount(rec[other, :, 0]).argmax()
+    bad_at = np.array([5, 300, 599])
+    rec[other, bad_at, 0] = [S * ld, hot_cell + (1 << 16), 0xFFFFFFFF]  # 1 << 16 > S * ld: same low 16 bits, out of range
+    valid = rec.copy()
+    valid[other, bad_at, 1] = np.float32(-0.0).view(np.uint32)  # x + -0.0 == x bit for bit: the record adds nothing
+    valid[other, bad_at, 0] = 0
+    uniq, acc, sorted_valid = _expected(lambda cells: q0[cells // ld, cells % ld], valid, count, rank)
+    want = q0.copy()
+    want[uniq // ld, uniq % ld] = acc
+    if entry == "gathered":
+        buf = _DevBuf(rec)
+        _lib.check(lib.qe_delta_apply_gathered_dev(algo.handle, buf.ptr, count, count, world, rank))
+    elif entry == "sorted":  # host-sorted by the full 32-bit cell: the bad records come last
+        others = rec[other]
+        buf = _DevBuf(np.ascontiguousarray(others[np.argsort(others[:, 0], kind="stable")]))
+        _lib.check(lib.qe_delta_apply_sorted_dev(algo.handle, buf.ptr, count))
+    elif entry == "skip":
+        buf = _DevBuf(rec)
+        _lib.check(lib.qe_delta_apply_skip_dev(algo.handle, buf.ptr, world * count, rank * count, (rank + 1) * count))
+    else:
+        buf = _DevBuf(np.ascontiguousarray(rec[other]))
+        _lib.check(lib.qe_delta_apply_dev(algo.handle, buf.ptr, count))
+    assert lib.qe_synchronize(algo.handle) == _lib.ERR_INDEX
+    assert b"3 delta records" in lib.qe_last_error()
+    _lib.check(lib.qe_synchronize(algo.handle))  # reported once
+    got = np.asarray(algo.q_table)
+    if entry in ("gathered", "sorted"):
+        assert np.array_equal(got, want)
+    else:  # float atomics in arrival order: the same sums in another order -- at most ~30 additions of |x| < 4 into a
+        # cell, each rounding by 2^-24 relative: 30 * 4 * 6e-8 < 1e-5
+        assert np.allclose(got, want, rtol=0, atol=1e-5)
+        untouched = np.ones((S, A), dtype=bool)
+        untouched[uniq // ld, uniq % ld] = False
+        assert np.array_equal(got[untouched], q0[untouched])
+    buf.free()
+
+
+def test_table_of_more_than_2_to_32_cells_is_refused():
+    """Records hold the cell in 32 bits.  No engine whose table has 2^32 cells or more (S = 2^28 + 1, A = 16: 17.2 GB of
+    float32, which would fit the device) can exist -- qe_create refuses it before anything is allocated -- so neither the
+    log nor an apply entry point can meet a cell it would have to truncate."""
+    _lib, Algo, _, _, _ = _product()
+    lib = _lib.load()
+    for S, A in (((1 << 28) + 1, 16), (1 << 28, 16), ((1 << 30) // 9 + 1, 33)):  # 33 actions: rows padded beyond 33
+        h = C.c_void_p()
+        assert lib.qe_create(C.byref(h), S, A, 0.99, 0, _lib.QE_F32, 0) == _lib.ERR_UNSUPPORTED, (S, A)
+        assert not h.value
+    with pytest.raises(NotImplementedError):
+        Algo((1 << 28) + 1, 16, 0.99, seed=0)
+
+
 @pytest.mark.parametrize(("n", "S", "A", "steps"), [(8192, 10_000_000, 32, 120), (4096, 1_000_000, 16, 150)])
 def test_turnstile_path_with_a_quarter_of_the_chip_taken(n, S, A, steps):
     """The turnstile kernel's workgroups wait for each other inside one launch, so all of them must be resident; the

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 
-def _worker(rank, world, port, out_dir, N_PER_RANK, S, A, SYNC, CHUNKS):
+def _worker(rank, world, port, out_dir, N_PER_RANK, S, A, SYNC, CHUNKS, path="auto", mode="iter", deterministic=True):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     import torch
     import torch.distributed as dist
@@ -30,25 +30,54 @@ def _worker(rank, world, port, out_dir, N_PER_RANK, S, A, SYNC, CHUNKS):
     from dist_classicrl_amd.environments import HashTabularEnv
     from dist_classicrl_amd.schedules import ConstantSchedule
 
+    from dist_classicrl_amd import _lib
+
     algo = OptimalQLearningBase(S, A, 0.99, seed=0)
+    if path == "wide_listed":  # the compacted-list walk of wide mode (automatic from 16 384 agents)
+        algo.set_rollout_path("wide")
+        algo.set_engine_option(_lib.OPT_LISTED_MIN_AGENTS, 1)
+        algo.set_engine_option(_lib.OPT_TOKEN_ROUNDS, 7)
     env = HashTabularEnv(N_PER_RANK, S, A, seed=1, agent_offset=rank * N_PER_RANK)
-    rt = GpuRolloutQLearning(algo, ConstantSchedule(0.1), ConstantSchedule(0.2))
+    rt = GpuRolloutQLearning(algo, ConstantSchedule(0.1), ConstantSchedule(0.2), learn_mode=mode)
     rt.sync_every = SYNC
-    rt.delta_sync = attach_engine(algo, SYNC, N_PER_RANK)
+    rt.delta_sync = attach_engine(algo, SYNC, N_PER_RANK, deterministic=deterministic)
     rt.trace_actions = None
     _, history, _, sd = rt.run_steps(SYNC * CHUNKS, env, None)
     np.save(os.path.join(out_dir, f"q{rank}.npy"), np.asarray(algo.q_table))
     np.save(os.path.join(out_dir, f"obs{rank}.npy"), sd["states"])
     np.save(os.path.join(out_dir, f"meta{rank}.npy"), np.array([rt.delta_sync.syncs, rt.delta_sync.bytes_exchanged]))
+    paths = sorted({_lib.decode_variant(v)["path"] for v in rt.last_stats["kernel_variants"]})
+    with open(os.path.join(out_dir, f"path{rank}.txt"), "w") as f:
+        f.write(",".join(paths))
     dist.destroy_process_group()
 
 
 @pytest.mark.parametrize(("world", "N_PER_RANK", "S", "A", "SYNC", "CHUNKS"), [
     (2, 96, 4000, 8, 20, 4),        # persistent kernel per rank
     (3, 96, 4000, 8, 20, 3),        # three ranks: the middle one skips its own segment of the gathered log
-    (2, 2100, 200000, 8, 10, 3),    # wide step-wise path per rank
+    (2, 2100, 200000, 8, 10, 3),    # 2100 agents per rank: the turnstile kernel (automatic choice)
 ])
 def test_ranks_sharing_one_gpu_match_the_simulated_protocol(tmp_path, world, N_PER_RANK, S, A, SYNC, CHUNKS):
+    _ranks_match_the_simulation(tmp_path, world, N_PER_RANK, S, A, SYNC, CHUNKS,
+                                "persistent" if N_PER_RANK <= 512 else "turnstile")
+
+
+@pytest.mark.parametrize(("world", "N_PER_RANK", "S", "A", "SYNC", "CHUNKS", "want_path", "path", "mode", "deterministic"), [
+    (2, 4096, 1_000_000, 16, 10, 3, "turnstile", "auto", "iter", True),  # the kernel a C3 rank / a C4 shard runs
+    (2, 4096, 1_000_000, 16, 10, 3, "turnstile", "auto", "vec", True),   # ... learn_vec: CHashRollout(mode="vec") records
+    (2, 2100, 200000, 8, 10, 3, "wide", "wide_listed", "iter", True),    # listed walk of wide mode
+    (3, 300, 4000, 8, 20, 3, "persistent", "auto", "iter", True),        # generic persistent build (129..512 agents)
+    (2, 96, 4000, 8, 20, 4, "persistent", "auto", "iter", 1),            # deterministic=1 means True, not float atomics
+])
+def test_ranks_on_the_paths_the_sharded_configurations_take(tmp_path, world, N_PER_RANK, S, A, SYNC, CHUNKS, want_path, path,
+                                                            mode, deterministic):
+    """The same protocol, bit for bit, where it had never run: the turnstile kernel (both update semantics), the
+    listed walk of wide mode, the generic persistent build, and an integer for ``deterministic``."""
+    _ranks_match_the_simulation(tmp_path, world, N_PER_RANK, S, A, SYNC, CHUNKS, want_path, path, mode, deterministic)
+
+
+def _ranks_match_the_simulation(tmp_path, world, N_PER_RANK, S, A, SYNC, CHUNKS, want_path, path="auto", mode="iter",
+                                deterministic=True):
     torch = pytest.importorskip("torch")
     import torch.multiprocessing as mp
 
@@ -57,8 +86,11 @@ def test_ranks_sharing_one_gpu_match_the_simulated_protocol(tmp_path, world, N_P
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    mp.spawn(_worker, args=(world, port, str(tmp_path), N_PER_RANK, S, A, SYNC, CHUNKS), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, port, str(tmp_path), N_PER_RANK, S, A, SYNC, CHUNKS, path, mode, deterministic),
+             nprocs=world, join=True)
     ranks = range(world)
+    for r in ranks:
+        assert (tmp_path / f"path{r}.txt").read_text() == want_path
     got = [np.load(tmp_path / f"q{r}.npy") for r in ranks]
     obs = [np.load(tmp_path / f"obs{r}.npy") for r in ranks]
     for r in ranks:
@@ -68,7 +100,7 @@ def test_ranks_sharing_one_gpu_match_the_simulated_protocol(tmp_path, world, N_P
     # simulation: each rank's records are its per-agent increments in (step, agent) order -- the content of
     # the engine's delta log; the other ranks add them one chunk late (overlap) and at the final flush,
     # rank by rank, each in slot order (= per cell: (rank, slot) order, the engine's sorted apply)
-    runs = [c_oracle.CHashRollout(N_PER_RANK, S, A, agent_offset=r * N_PER_RANK, dtype=np.float32) for r in ranks]
+    runs = [c_oracle.CHashRollout(N_PER_RANK, S, A, agent_offset=r * N_PER_RANK, dtype=np.float32, mode=mode) for r in ranks]
     eps, lr = np.full(SYNC, 0.2), np.full(SYNC, 0.1)
 
     def apply_others(recs):
