@@ -33,15 +33,22 @@ OPT_TURN_POLL = 8
 OPT_STAMP_HASH_BITS = 9
 PATH_AUTO, PATH_STEPWISE, PATH_PERSISTENT, PATH_WIDE, PATH_TURNSTILE = 0, 1, 2, 3, 4
 
+RULE_Q_LEARNING, RULE_SARSA, RULE_EXPECTED_SARSA = 0, 1, 2  # qe_update_rule
+UPDATE_RULES = {"q_learning": RULE_Q_LEARNING, "sarsa": RULE_SARSA, "expected_sarsa": RULE_EXPECTED_SARSA}
+
 ERR_INVALID, ERR_NO_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INDEX = -1, -2, -3, -4, -5
 
 
 def decode_variant(v: int) -> dict:
-    """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h)."""
+    """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h).  ``rule``: the population's update rule
+    -- path 8 (``population_td``, kernel ``k_rollout_runs_td``) carries it in bits 4-5, where the persistent path keeps
+    ``lean``; every other path learns with Q-learning."""
     v = int(v)
+    td = (v & 15) == 8
     return {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
-                 7: "population_eval"}.get(v & 15, "none"),
+                 7: "population_eval", 8: "population_td"}.get(v & 15, "none"),
+        "rule": {1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td else "q_learning",
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
         "cap512": bool((v >> 9) & 1), "dataflow": bool((v >> 10) & 1), "nv": (v >> 12) & 255, "masked": bool((v >> 20) & 1),
     }
@@ -188,6 +195,10 @@ PROTOTYPES = {
     "qe_population_log": (C.c_int64, [_P, C.c_int64, _I32P, _F32P]),
     "qe_population_step_counters": (C.c_int, [_P, _U64P]),
     "qe_population_set_step_counters": (C.c_int, [_P, _U64P]),
+    "qe_population_set_update_rule": (C.c_int, [_P, C.c_int32]),
+    "qe_population_update_rule": (C.c_int, [_P]),
+    "qe_population_pending_actions": (C.c_int, [_P, _I32P]),
+    "qe_population_set_pending_actions": (C.c_int, [_P, _I32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_replay_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "qe_replay_destroy": (C.c_int, [_P]),

@@ -18,6 +18,12 @@ Greedy evaluation (``evaluate_steps`` / ``evaluate_episodes``, kernel ``k_evalua
 contract: run ``r`` is the standalone runtime's ``evaluate_steps`` / ``evaluate_episodes`` / ``train`` of that one-agent
 run.  Each run keeps its own draw counter (``step_counters``): an episode-based evaluation advances run ``r`` by the
 steps it took, as the standalone ``evaluate_episodes`` does, so later training still draws what the standalone run draws.
+
+``update_rule`` chooses the TD target of every run (one rule per population): ``"q_learning"`` (the default, and the
+contract above), ``"sarsa"`` or ``"expected_sarsa"`` (kernel ``k_rollout_runs_td``).  The reference has no on-policy
+rule to equal; DESIGN section 4.3c defines both, and ``tests/td_rules_model.py`` restates that definition on the oracle.
+A SARSA run has chosen its next action when a call returns: ``state_dict["pending_actions"]`` carries it to the next
+call (or process), so the chaining contract holds for every rule.
 """
 
 from __future__ import annotations
@@ -113,6 +119,18 @@ class PopulationTraining(NamedTuple):
         return self.returns[self.offsets[r]:self.offsets[r + 1]]
 
 
+def pending_array(values, runs) -> np.ndarray | None:
+    """``pending_actions`` of a state dict as the int32 ``[runs]`` array the library takes (None: no run has one);
+    ``ValueError`` on any other shape."""
+    if values is None:
+        return None
+    arr = np.asarray(values)
+    if arr.shape != (runs,) or arr.dtype.kind not in "iu":
+        msg = f"pending_actions: expected {runs} integers, got shape {arr.shape} of {arr.dtype}"
+        raise ValueError(msg)
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
 def _per_run(value, runs, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != runs:
@@ -126,11 +144,12 @@ class QLearningPopulation:
     """``runs`` independent single-agent Q-learners over ``state_size`` x ``action_size`` (at most 64 actions).
 
     ``discount_factor``, ``lr_schedule`` and ``exploration_rate_schedule`` take one value / schedule for every run or a
-    sequence of ``runs``.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa") holds for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
-                 exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0):
+                 exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
+                 update_rule="q_learning"):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -144,6 +163,10 @@ class QLearningPopulation:
         if self.runs <= 0:
             msg = "runs must be positive"
             raise ValueError(msg)
+        if update_rule not in _lib.UPDATE_RULES:
+            msg = f"update_rule must be one of {', '.join(map(repr, _lib.UPDATE_RULES))}, got {update_rule!r}"
+            raise ValueError(msg)
+        self.update_rule = update_rule
         self.learn_mode = learn_mode
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.discount_factor = np.ascontiguousarray(_per_run(discount_factor, self.runs, "discount_factor"), dtype=np.float64)
@@ -159,6 +182,8 @@ class QLearningPopulation:
         _lib.check(self._lib.qe_create_population(C.byref(self._h), self.runs, self.state_size, self.action_size, self.seed,
                                                   _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64, int(device)))
         _lib.check(self._lib.qe_population_configure(self._h, None, None, _lib.ptr(self.discount_factor, C.c_double)))
+        if update_rule != "q_learning":
+            _lib.check(self._lib.qe_population_set_update_rule(self._h, _lib.UPDATE_RULES[update_rule]))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -203,6 +228,18 @@ class QLearningPopulation:
         out = np.empty(self.runs, dtype=np.uint64)
         _lib.check(self._lib.qe_population_step_counters(self._h, _lib.ptr(out, C.c_uint64)))
         return out
+
+    @property
+    def pending_actions(self) -> np.ndarray:
+        """SARSA: the action each run has already chosen for its next training step, int32 ``[runs]``, -1 = none (the
+        run picks at that step).  Other rules: all -1."""
+        out = np.empty(self.runs, dtype=np.int32)
+        _lib.check(self._lib.qe_population_pending_actions(self._h, _lib.ptr(out, C.c_int32)))
+        return out
+
+    @pending_actions.setter
+    def pending_actions(self, values) -> None:
+        _lib.check(self._lib.qe_population_set_pending_actions(self._h, _lib.ptr(pending_array(values, self.runs), C.c_int32)))
 
     def _rng_step(self):
         """``state_dict["rng_step"]``: an int while all runs agree, else the int64 array of every run's."""
@@ -272,7 +309,8 @@ class QLearningPopulation:
 
     def run_steps(self, steps, env, curr_state_dict=None, log=True) -> PopulationRun:
         """``steps`` steps of every run on ``env`` (a device environment of ``num_agents == runs``).  ``curr_state_dict``
-        None resets the environment, as the reference's ``run_steps``; the dict of the previous call continues it.
+        None resets the environment, as the reference's ``run_steps``; the dict of the previous call continues it
+        (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step).
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
         result, in which the other runs are unaffected)."""
@@ -283,6 +321,8 @@ class QLearningPopulation:
             env.reset_device()
         elif not env.is_resident(curr_state_dict):
             env.restore(curr_state_dict["states"], curr_state_dict["rewards"], curr_state_dict.get("aux"))
+        if self.update_rule == "sarsa":
+            self.pending_actions = None if curr_state_dict is None else curr_state_dict.get("pending_actions")
         eps_d = self._descriptors(self.exploration_rate_schedules)
         lr_d = self._descriptors(self.lr_schedules)
         sched_p = C.POINTER(_lib.RunSchedule)
@@ -321,6 +361,8 @@ class QLearningPopulation:
         state_dict["rng_step"] = self._rng_step()
         state_dict["lr"] = lr_v
         state_dict["exploration_rate"] = eps_v
+        if self.update_rule == "sarsa":
+            state_dict["pending_actions"] = self.pending_actions
         result = PopulationRun(means, counts, rets, offsets, at, state_dict)
         if empty:
             bad = np.flatnonzero(status).tolist()
@@ -332,7 +374,10 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter(s) and every run's schedule values.  Tables: :meth:`load`; environments: pass the dict to ``run_steps``."""
+        counter(s), every run's schedule values and (SARSA) pending action.  Tables: :meth:`load`; environments: pass
+        the dict to ``run_steps``."""
+        if self.update_rule == "sarsa":
+            self.pending_actions = state_dict.get("pending_actions")
         rng_step = state_dict["rng_step"]
         if np.ndim(rng_step) == 0:
             self.step_counter = int(rng_step)
@@ -463,4 +508,4 @@ class QLearningPopulation:
 
 
 __all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "schedule_descriptor"]
+           "pending_array", "schedule_descriptor"]

@@ -173,12 +173,16 @@ struct PopState {
     DevBuf<long long> used;            // greedy evaluation, episode mode: steps each run took in the call ...
     DevBuf<uint8_t> done;              // ... and whether it has reached its episode count
     PinnedBuf<uint8_t> h_done;
+    // Update rule of every run (qe_update_rule).  SARSA carries the action chosen for a run's next step from launch to
+    // launch and call to call: pending[r], -1 = none (allocated on first use; k_rollout_runs_td, qe_rollout_runs_td.h).
+    int rule = QE_RULE_Q_LEARNING;
+    DevBuf<int32_t> pending;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
         seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
         h_cnt.release(); h_step.release(); h_ret.release();
-        step_off.release(); used.release(); done.release(); h_done.release();
+        step_off.release(); used.release(); done.release(); h_done.release(); pending.release();
         off_any = false;
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -395,13 +399,15 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   wavefronts), bit 7 FULL (every lane an agent), bit 8 SEQ (built without the general ordered path), bit 9 the
 //   512-agent build, bit 10 the dataflow kernel (k_rollout_df), bits 12-19 NV (16-byte loads per fp32 row), bit 20
 //   masked environment; path 6 = population (k_rollout_runs) and path 7 = population greedy evaluation
-//   (k_evaluate_runs), both with the same NV and masked bits
+//   (k_evaluate_runs), both with the same NV and masked bits; path 8 = population with an on-policy update rule
+//   (k_rollout_runs_td): those NV and masked bits, and the rule (qe_update_rule) in bits 4-5
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
                   QE_VARIANT_EVAL = (int64_t)RolloutPath::Eval;
 constexpr int64_t QE_VARIANT_RUNS = 6;  // population path (k_rollout_runs): bits 12-19 NV, bit 20 masked, as persistent
 constexpr int64_t QE_VARIANT_RUNS_EVAL = 7;  // population greedy evaluation (k_evaluate_runs): the same NV and masked bits
+constexpr int64_t QE_VARIANT_RUNS_TD = 8;  // population, SARSA / Expected SARSA (k_rollout_runs_td): + the rule in bits 4-5
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -410,9 +416,35 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
+// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+template <class Env, class F>
+inline int64_t runs_by_build(int ld, bool masked, F go) {
+    using Yes = std::true_type;
+    using No = std::false_type;
+    if constexpr (std::is_same<Env, HashEnv>::value || std::is_same<Env, TableEnv>::value) {  // any A, masked or not
+        auto by_mask = [&](auto nv) { return masked ? go(nv, Yes{}) : go(nv, No{}); };
+        switch (ld) {  // a power of two (row_stride), at most 64
+            case 4: return by_mask(std::integral_constant<int, 1>{});
+            case 8: return by_mask(std::integral_constant<int, 2>{});
+            case 16: return by_mask(std::integral_constant<int, 4>{});
+            case 32: return by_mask(std::integral_constant<int, 8>{});
+            default: return by_mask(std::integral_constant<int, 16>{});
+        }
+    } else if constexpr (std::is_same<Env, TttEnv>::value) {
+        return go(std::integral_constant<int, 4>{}, Yes{});  // A = 9 -> row stride 16
+    } else {
+        return go(std::integral_constant<int, 1>{}, No{});  // GridLake (A = 4) and the bandit (A = 2)
+    }
+}
+
 // population path: one launch of `steps` steps of every run (qe_inst_runs.hip); returns its kernel_variant
 template <typename T, class Env>
 int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps);
+// ... with the update rule `rule` (QE_RULE_SARSA: `pending` holds every run's pending action; QE_RULE_EXPECTED_SARSA),
+// qe_inst_runs_td.hip; a build the rule is not compiled for returns QE_ERR_UNSUPPORTED (see runs_td_supported)
+template <typename T, class Env>
+int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
+                       int32_t* pending);
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,

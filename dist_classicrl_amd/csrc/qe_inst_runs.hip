@@ -8,36 +8,11 @@
 #error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
 #endif
 
-namespace {
-
-// The (NV, masked) build of a row stride: go(integral_constant<int, NV>, bool_constant<masked>).
-template <class Env, class F>
-int64_t by_build(int ld, bool masked, F go) {
-    using Yes = std::true_type;
-    using No = std::false_type;
-    if constexpr (std::is_same<Env, HashEnv>::value || std::is_same<Env, TableEnv>::value) {  // any A, masked or not
-        auto by_mask = [&](auto nv) { return masked ? go(nv, Yes{}) : go(nv, No{}); };
-        switch (ld) {  // a power of two (row_stride), at most 64
-            case 4: return by_mask(std::integral_constant<int, 1>{});
-            case 8: return by_mask(std::integral_constant<int, 2>{});
-            case 16: return by_mask(std::integral_constant<int, 4>{});
-            case 32: return by_mask(std::integral_constant<int, 8>{});
-            default: return by_mask(std::integral_constant<int, 16>{});
-        }
-    } else if constexpr (std::is_same<Env, TttEnv>::value) {
-        return go(std::integral_constant<int, 4>{}, Yes{});  // A = 9 -> row stride 16
-    } else {
-        return go(std::integral_constant<int, 1>{}, No{});  // GridLake (A = 4) and the bandit (A = 2)
-    }
-}
-
-}  // namespace
-
 // One launch of `steps` steps of every run; returns the kernel_variant of the build (QE_VARIANT_RUNS | NV | masked).
 template <typename T, class Env>
 int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps) {
     const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
+    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
         constexpr int NV = decltype(nv)::value;
         constexpr bool MK = decltype(mk)::value;
         hipLaunchKernelGGL((k_rollout_runs<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps);
@@ -50,7 +25,7 @@ template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
                              long long episodes, long long* used, uint8_t* done) {
     const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
+    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
         constexpr int NV = decltype(nv)::value;
         constexpr bool MK = decltype(mk)::value;
         hipLaunchKernelGGL((k_evaluate_runs<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps, episodes, used, done);

@@ -1,5 +1,6 @@
 // qe_population.hip -- host side of the population path (include/qlearn_engine.h, "population"): M independent
-// single-agent runs in one [M * S, ld] table, trained by k_rollout_runs and evaluated greedily by k_evaluate_runs
+// single-agent runs in one [M * S, ld] table, trained by k_rollout_runs (Q-learning) or k_rollout_runs_td (SARSA, Expected
+// SARSA: qe_rollout_runs_td.h, instantiated in qe_inst_runs_td.hip) and evaluated greedily by k_evaluate_runs
 // (qe_rollout_runs.h, instantiated in qe_inst_runs.hip), plus the compaction of the per-run episode-log segments and
 // the per-run draw counters.
 #include "qe_host.h"
@@ -179,6 +180,16 @@ int set_counters(qe_engine* e, const uint64_t* in) {
     return QE_OK;
 }
 
+// SARSA's pending actions: allocated on first use, every run without one.
+int pending_reserve(qe_engine* e) {
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    if (P.pending.p) return QE_OK;
+    HIP_TRY(P.pending.ensure(m));
+    HIP_TRY(hipMemsetAsync(P.pending.p, 0xFF, m * sizeof(int32_t), e->stream));  // -1
+    return QE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -279,6 +290,8 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
     const bool masked = env->p.masked != 0 || env->p.kind == QE_ENV_TICTACTOE;
     const int nan_select = masked && e->A > 10 ? 1 : 0;
     const EnvCtx ev = make_envctx(e, env);
+    if (P.rule == QE_RULE_SARSA)
+        if (int rc = pending_reserve(e)) return rc;
     CallLog L;
     int64_t launches = 0, variant = QE_VARIANT_RUNS;
     HIP_TRY(hipEventRecord(P.ev0, e->stream));
@@ -298,6 +311,8 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.mode = mode; c.nan_select = nan_select;
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
+                if (P.rule != QE_RULE_Q_LEARNING)
+                    return launch_runs_td<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p);
                 return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
             };
             return e->dtype == QE_F32 ? go(float{}) : go(double{});
@@ -459,6 +474,48 @@ int qe_population_set_step_counters(qe_engine* e, const uint64_t* in) {
     if (!in) return qe_fail(QE_ERR_INVALID, "in is NULL");
     HIP_TRY(hipSetDevice(e->device));
     return set_counters(e, in);
+}
+
+int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
+    if (int rc = need_population(e)) return rc;
+    if (rule != QE_RULE_Q_LEARNING && rule != QE_RULE_SARSA && rule != QE_RULE_EXPECTED_SARSA)
+        return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
+    e->pop.rule = rule;
+    return QE_OK;
+}
+
+int qe_population_update_rule(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    return e->pop.rule;
+}
+
+int qe_population_pending_actions(qe_engine* e, int32_t* out) {
+    if (int rc = need_population(e)) return rc;
+    if (!out) return qe_fail(QE_ERR_INVALID, "out is NULL");
+    const size_t m = (size_t)e->pop.runs;
+    if (!e->pop.pending.p) {  // never set, never run under SARSA: none
+        std::fill(out, out + m, -1);
+        return QE_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(out, e->pop.pending.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_set_pending_actions(qe_engine* e, const int32_t* in) {
+    if (int rc = need_population(e)) return rc;
+    const size_t m = (size_t)e->pop.runs;
+    for (size_t r = 0; in && r < m; ++r)  // (the kernel indexes the run's row with it)
+        if (in[r] < -1 || in[r] >= e->A)
+            return qe_fail(QE_ERR_INVALID, "pending action of run %lld: %d is outside [-1, %d)", (long long)r, (int)in[r], (int)e->A);
+    if (!in && !e->pop.pending.p) return QE_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = pending_reserve(e)) return rc;
+    if (in) HIP_TRY(hipMemcpyAsync(e->pop.pending.p, in, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(e->pop.pending.p, 0xFF, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
 }
 
 int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret) {

@@ -91,7 +91,9 @@ typedef struct qe_rollout_stats {
                                 bit 10 the dataflow kernel (sharers of a row ordered by value hand-over in LDS),
                                 bits 12-19 16-byte loads per row, bit 20 masked environment (tests assert on these);
                                 path 6: population (qe_population_rollout), path 7: population greedy evaluation
-                                (qe_population_evaluate), both with the same NV and masked bits */
+                                (qe_population_evaluate), both with the same NV and masked bits; path 8: population with
+                                an on-policy update rule (SARSA / Expected SARSA): those NV and masked bits, and the rule
+                                (qe_update_rule) in bits 4-5 */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -320,7 +322,20 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         the first `cap` entries; returns the count.
  *   qe_population_step_counters / qe_population_set_step_counters  every run's draw counter (`runs` entries).  Each
  *                         call of the rollout or of a step-mode evaluation advances every run by `steps`; an
- *                         episode-mode evaluation advances run r by the steps it took, so the counters may differ. */
+ *                         episode-mode evaluation advances run r by the steps it took, so the counters may differ.
+ *   qe_population_set_update_rule  the TD target of every run of the population (one rule per population):
+ *                         Q-learning (the default) bootstraps from max Q[s', .]; SARSA from Q[s', a'] with a' the action
+ *                         the run takes next (chosen before the update, with the draws and epsilon of the next step);
+ *                         Expected SARSA from (1 - eps') * max + eps' * mean of Q[s', valid], eps' the next step's epsilon
+ *                         clamped to [0, 1].  Not a population engine or an unknown rule -> QE_ERR_INVALID.  Greedy
+ *                         evaluation does not depend on the rule.  qe_population_update_rule returns the rule (or a
+ *                         negative qe_status).
+ *   qe_population_pending_actions / qe_population_set_pending_actions  SARSA's run state besides the tables: the action
+ *                         already chosen for each run's next step (`runs` entries, -1 = none: the run picks at its next
+ *                         step).  The rollout leaves it behind; set it (NULL: none for every run) when the environment
+ *                         state is restored or reset.  Entries outside [-1, action_size) -> QE_ERR_INVALID.  Other rules
+ *                         neither read nor write it. */
+enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
 typedef struct qe_run_schedule {
     double value;      /* the value read at the next step */
@@ -342,6 +357,10 @@ int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t
 int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret);
 int qe_population_step_counters(qe_engine* e, uint64_t* out);
 int qe_population_set_step_counters(qe_engine* e, const uint64_t* in);
+int qe_population_set_update_rule(qe_engine* e, int32_t rule);
+int qe_population_update_rule(qe_engine* e);
+int qe_population_pending_actions(qe_engine* e, int32_t* out);
+int qe_population_set_pending_actions(qe_engine* e, const int32_t* in);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

@@ -2,12 +2,17 @@
 rollout on the same environment, measured in the same process.
 
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
+                                    [--rule q_learning|sarsa|expected_sarsa] [--actions A]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
 M = 4096.  Rate = M x steps / wall time of one timed call (after a warm-up call; the call returns after the device has
 finished).  Writes DIR/population_rate.json and prints one line per workload.  For kernel time and bytes per env-step,
 run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/population_rate.py --out DIR --quick`.
+
+--rule trains with that update rule (k_rollout_runs_td for sarsa / expected_sarsa; the standalone baseline is always
+the Q-learning one-agent rollout) and writes DIR/population_rate_<rule>.json for a rule other than q_learning.
+--actions A adds a HashTabularEnv of 1e4 states x A actions at M = 4096 (the wide-row builds: A = 64 is NV = 16).
 
 --evaluate measures greedy evaluation instead (QLearningPopulation.evaluate_steps, k_evaluate_runs) on the same
 workloads and M values, against the standalone one-agent evaluate_steps, after 200 training steps, and writes
@@ -63,9 +68,10 @@ def schedules():
     return ExponentialSchedule(0.1, 1e-3, 0.9995), ExponentialSchedule(1.0, 0.05, 0.9995)
 
 
-def population_rate(make_env, M, S, A, steps, dtype, log):
+def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning"):
     lr, eps = schedules()
-    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype)
+    kw = {} if rule == "q_learning" else {"update_rule": rule}
+    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
     t0 = time.perf_counter()
@@ -124,7 +130,12 @@ def main() -> None:
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--quick", action="store_true", help="fewer steps and shapes (profiling runs)")
     ap.add_argument("--evaluate", action="store_true", help="greedy evaluation (evaluate_steps) instead of training")
+    ap.add_argument("--rule", choices=["q_learning", "sarsa", "expected_sarsa"], default="q_learning",
+                    help="update rule of the trained population (not with --evaluate: evaluation does not depend on it)")
+    ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
+    if args.evaluate and args.rule != "q_learning":
+        ap.error("--rule applies to training runs only")
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
     P, isd = frozen_lake_8x8_slippery()
@@ -141,14 +152,20 @@ def main() -> None:
     plan = [("frozenlake8x8", lake, 64, 4, M, steps, log) for M in ((4096, 65536) if args.quick else (64, 1024, 4096, 65536))
             for log in (True, False)]
     plan += [("tictactoe", ttt, 19683, 9, 1024, steps // 5, True), ("hash1e4x8", hashed, 10000, 8, 4096, steps, True)]
+    if args.actions:
+        plan.append((f"hash1e4x{args.actions}", lambda n: HashTabularEnv(n, 10000, args.actions, seed=1), 10000, args.actions,
+                     4096, steps, True))
     base_cache = {}
     lines = []
     for name, make_env, S, A, M, k, log in plan:
         if name not in base_cache:
             base_cache[name] = (standalone_eval_rate if args.evaluate else standalone_rate)(make_env, S, A, min(k, 5000), dtype)
-        pop = (population_eval_rate if args.evaluate else population_rate)(make_env, M, S, A, k, dtype, log)
+        if args.evaluate:
+            pop = population_eval_rate(make_env, M, S, A, k, dtype, log)
+        else:
+            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule)
         base = base_cache[name]
-        line = {"workload": name, "evaluate": args.evaluate, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
+        line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
                 "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
         lines.append(line)
         print(f"{name:14s} M={M:6d} log={int(log)} {pop['env_steps_per_s'] / 1e6:10.1f} M env-steps/s "
@@ -156,6 +173,8 @@ def main() -> None:
               f"{pop['launches']} launches, kernel {pop['kernel_ms']:.1f} ms)", flush=True)
     args.out.mkdir(parents=True, exist_ok=True)
     name = "population_eval_rate.json" if args.evaluate else "population_rate.json"
+    if args.rule != "q_learning":
+        name = f"population_rate_{args.rule}.json"
     (args.out / name).write_text(json.dumps(lines, indent=1))
 
 
