@@ -42,12 +42,13 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INDEX = -1, -2, -3, -4
 def decode_variant(v: int) -> dict:
     """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h).  ``rule``: the population's update rule
     -- path 8 (``population_td``, kernel ``k_rollout_runs_td``) carries it in bits 4-5, where the persistent path keeps
-    ``lean``; every other path learns with Q-learning."""
+    ``lean``; every other path learns with Q-learning.  Paths 9 and 10 (``population_double``, kernel ``k_double_rollout``,
+    and ``population_double_eval``, ``k_double_evaluate``) are the population with the double estimator."""
     v = int(v)
     td = (v & 15) == 8
     return {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
-                 7: "population_eval", 8: "population_td"}.get(v & 15, "none"),
+                 7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval"}.get(v & 15, "none"),
         "rule": {1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td else "q_learning",
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
         "cap512": bool((v >> 9) & 1), "dataflow": bool((v >> 10) & 1), "nv": (v >> 12) & 255, "masked": bool((v >> 20) & 1),
@@ -199,6 +200,11 @@ PROTOTYPES = {
     "qe_population_update_rule": (C.c_int, [_P]),
     "qe_population_pending_actions": (C.c_int, [_P, _I32P]),
     "qe_population_set_pending_actions": (C.c_int, [_P, _I32P]),
+    "qe_population_set_double": (C.c_int, [_P, C.c_int32]),
+    "qe_population_double": (C.c_int, [_P]),
+    "qe_population_table_b_upload": (C.c_int, [_P, _P, C.c_int32]),
+    "qe_population_table_b_download": (C.c_int, [_P, _P, C.c_int32]),
+    "qe_population_table_b_download_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_replay_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "qe_replay_destroy": (C.c_int, [_P]),

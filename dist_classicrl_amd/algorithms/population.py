@@ -24,6 +24,12 @@ contract above), ``"sarsa"`` or ``"expected_sarsa"`` (kernel ``k_rollout_runs_td
 rule to equal; DESIGN section 4.3c defines both, and ``tests/td_rules_model.py`` restates that definition on the oracle.
 A SARSA run has chosen its next action when a call returns: ``state_dict["pending_actions"]`` carries it to the next
 call (or process), so the chaining contract holds for every rule.
+
+``double_q=True`` turns Q-learning into Double Q-learning (van Hasselt 2010; kernels ``k_double_rollout`` /
+``k_double_evaluate``): every run owns two tables, A (``q_tables``) and B (``q_tables_b``), acts on their sum, and each
+step updates the one a coin names with the other's value at its own arg-max -- the cure for the maximisation bias of
+``max_a' Q[s', a']``.  The coin is the unused fourth word of the step's policy draws, so there is no new run state
+besides B.  DESIGN section 4.3c defines the step; ``tests/double_q_model.py`` restates it on the oracle.
 """
 
 from __future__ import annotations
@@ -144,12 +150,13 @@ class QLearningPopulation:
     """``runs`` independent single-agent Q-learners over ``state_size`` x ``action_size`` (at most 64 actions).
 
     ``discount_factor``, ``lr_schedule`` and ``exploration_rate_schedule`` take one value / schedule for every run or a
-    sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa") holds for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa") and ``double_q`` (two tables per
+    run, Q-learning only) hold for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
-                 update_rule="q_learning"):
+                 update_rule="q_learning", double_q=False):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -166,7 +173,11 @@ class QLearningPopulation:
         if update_rule not in _lib.UPDATE_RULES:
             msg = f"update_rule must be one of {', '.join(map(repr, _lib.UPDATE_RULES))}, got {update_rule!r}"
             raise ValueError(msg)
+        if double_q and update_rule != "q_learning":
+            msg = f"double_q=True is Double Q-learning: it needs update_rule='q_learning', got {update_rule!r}"
+            raise ValueError(msg)
         self.update_rule = update_rule
+        self.double_q = bool(double_q)
         self.learn_mode = learn_mode
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.discount_factor = np.ascontiguousarray(_per_run(discount_factor, self.runs, "discount_factor"), dtype=np.float64)
@@ -184,6 +195,8 @@ class QLearningPopulation:
         _lib.check(self._lib.qe_population_configure(self._h, None, None, _lib.ptr(self.discount_factor, C.c_double)))
         if update_rule != "q_learning":
             _lib.check(self._lib.qe_population_set_update_rule(self._h, _lib.UPDATE_RULES[update_rule]))
+        if self.double_q:
+            _lib.check(self._lib.qe_population_set_double(self._h, 1))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -249,9 +262,34 @@ class QLearningPopulation:
     # ------------------------------------------------------------------ tables
     @property
     def q_tables(self) -> np.ndarray:
-        """All tables, ``(runs, state_size, action_size)``."""
+        """All tables, ``(runs, state_size, action_size)`` (``double_q``: the tables A)."""
         host = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
         _lib.check(self._lib.qe_table_download(self._h, host.ctypes.data, _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64))
+        return host
+
+    def _need_double(self) -> None:
+        if not self.double_q:
+            msg = "a population without double_q has no second table"
+            raise ValueError(msg)
+
+    @property
+    def q_tables_b(self) -> np.ndarray:
+        """``double_q``: all tables B, ``(runs, state_size, action_size)``."""
+        self._need_double()
+        host = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
+        _lib.check(self._lib.qe_population_table_b_download(self._h, host.ctypes.data,
+                                                            _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64))
+        return host
+
+    def q_table_b(self, r: int) -> np.ndarray:
+        """``double_q``: run ``r``'s table B, ``(state_size, action_size)``."""
+        self._need_double()
+        r = int(r)
+        if not 0 <= r < self.runs:
+            msg = f"run {r} out of range [0, {self.runs})"
+            raise IndexError(msg)
+        host = np.empty((self.state_size, self.action_size), dtype=self.dtype)
+        _lib.check(self._lib.qe_population_table_b_download_rows(self._h, host.ctypes.data, r * self.state_size, self.state_size))
         return host
 
     def q_table(self, r: int) -> np.ndarray:
@@ -264,8 +302,7 @@ class QLearningPopulation:
         _lib.check(self._lib.qe_table_download_rows(self._h, host.ctypes.data, r * self.state_size, self.state_size))
         return host
 
-    def set_q_tables(self, tables) -> None:
-        """``(state_size, action_size)`` (every run starts from it) or ``(runs, state_size, action_size)``."""
+    def _upload_form(self, tables):
         arr = np.asarray(tables)
         one = (self.state_size, self.action_size)
         if arr.shape == one:
@@ -274,15 +311,35 @@ class QLearningPopulation:
             msg = f"tables must have shape {one} or {(self.runs, *one)}, got {arr.shape}"
             raise ValueError(msg)
         up = np.float32 if arr.dtype == np.float32 else np.float64
-        arr = np.ascontiguousarray(arr, dtype=up)
-        _lib.check(self._lib.qe_table_upload(self._h, arr.ctypes.data, _lib.QE_F32 if up == np.float32 else _lib.QE_F64))
+        return np.ascontiguousarray(arr, dtype=up), _lib.QE_F32 if up == np.float32 else _lib.QE_F64
+
+    def set_q_tables(self, tables, tables_b=None) -> None:
+        """``(state_size, action_size)`` (every run starts from it) or ``(runs, state_size, action_size)``.
+        ``double_q``: ``tables`` are the tables A, ``tables_b`` (same shapes) the tables B; None leaves B as it is."""
+        if tables_b is not None:
+            self._need_double()
+        arr, code = self._upload_form(tables)
+        arr_b, code_b = (None, None) if tables_b is None else self._upload_form(tables_b)  # (both checked before either is sent)
+        _lib.check(self._lib.qe_table_upload(self._h, arr.ctypes.data, code))
+        if arr_b is not None:
+            _lib.check(self._lib.qe_population_table_b_upload(self._h, arr_b.ctypes.data, code_b))
 
     def save(self, filename) -> None:
-        """The ``(runs, state_size, action_size)`` tables as one ``.npy``."""
-        np.save(filename, self.q_tables)
+        """The ``(runs, state_size, action_size)`` tables as one ``.npy``; ``double_q``: ``(2, runs, state_size,
+        action_size)``, A then B."""
+        np.save(filename, np.stack([self.q_tables, self.q_tables_b]) if self.double_q else self.q_tables)
 
     def load(self, filename) -> None:
-        self.set_q_tables(np.load(filename))
+        """What :meth:`save` wrote (``double_q``: that four-dimensional shape and no other)."""
+        arr = np.load(filename)
+        if not self.double_q:
+            self.set_q_tables(arr)
+            return
+        want = (2, self.runs, self.state_size, self.action_size)
+        if arr.shape != want:
+            msg = f"a double_q population loads tables of shape {want}, got {arr.shape}"
+            raise ValueError(msg)
+        self.set_q_tables(arr[0], arr[1])
 
     # ------------------------------------------------------------------ training
     def _descriptors(self, schedules):

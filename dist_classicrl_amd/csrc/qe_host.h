@@ -177,12 +177,17 @@ struct PopState {
     // launch and call to call: pending[r], -1 = none (allocated on first use; k_rollout_runs_td, qe_rollout_runs_td.h).
     int rule = QE_RULE_Q_LEARNING;
     DevBuf<int32_t> pending;
+    // Double estimator (qe_population_set_double): table B, the engine's dtype, shape and row stride; the engine's own
+    // table is A.  NULL: off (k_double_rollout / k_double_evaluate, qe_rollout_double.h).
+    void* table_b = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
         seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
         h_cnt.release(); h_step.release(); h_ret.release();
         step_off.release(); used.release(); done.release(); h_done.release(); pending.release();
+        if (table_b) (void)hipFree(table_b);
+        table_b = nullptr;
         off_any = false;
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -400,7 +405,8 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   512-agent build, bit 10 the dataflow kernel (k_rollout_df), bits 12-19 NV (16-byte loads per fp32 row), bit 20
 //   masked environment; path 6 = population (k_rollout_runs) and path 7 = population greedy evaluation
 //   (k_evaluate_runs), both with the same NV and masked bits; path 8 = population with an on-policy update rule
-//   (k_rollout_runs_td): those NV and masked bits, and the rule (qe_update_rule) in bits 4-5
+//   (k_rollout_runs_td): those NV and masked bits, and the rule (qe_update_rule) in bits 4-5; path 9 = population with
+//   the double estimator (k_double_rollout) and path 10 = its greedy evaluation (k_double_evaluate), NV and masked bits
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -408,6 +414,8 @@ constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIA
 constexpr int64_t QE_VARIANT_RUNS = 6;  // population path (k_rollout_runs): bits 12-19 NV, bit 20 masked, as persistent
 constexpr int64_t QE_VARIANT_RUNS_EVAL = 7;  // population greedy evaluation (k_evaluate_runs): the same NV and masked bits
 constexpr int64_t QE_VARIANT_RUNS_TD = 8;  // population, SARSA / Expected SARSA (k_rollout_runs_td): + the rule in bits 4-5
+constexpr int64_t QE_VARIANT_RUNS_DOUBLE = 9;        // population, Double Q-learning (k_double_rollout): NV and masked bits
+constexpr int64_t QE_VARIANT_RUNS_DOUBLE_EVAL = 10;  // ... and its greedy evaluation (k_double_evaluate)
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -416,7 +424,7 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
-// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip): go(integral_constant<int, NV>, bool_constant<masked>).
 template <class Env, class F>
 inline int64_t runs_by_build(int ld, bool masked, F go) {
     using Yes = std::true_type;
@@ -449,6 +457,13 @@ int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev
 template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
                              long long episodes, long long* used, uint8_t* done);
+// ... and the double estimator (qe_inst_runs_double.hip): training and greedy evaluation over the tables c.q and table_b
+template <typename T, class Env>
+int64_t launch_double_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
+                           T* table_b);
+template <typename T, class Env>
+int64_t launch_double_evaluate(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
+                               long long episodes, long long* used, uint8_t* done, const T* table_b);
 // resident workgroups per CU of the k_step_turn build this engine would launch (occupancy query), 0 on failure
 template <typename T, class Env>
 int turn_occupancy(const qe_engine* e);

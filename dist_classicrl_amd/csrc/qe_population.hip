@@ -2,7 +2,9 @@
 // single-agent runs in one [M * S, ld] table, trained by k_rollout_runs (Q-learning) or k_rollout_runs_td (SARSA, Expected
 // SARSA: qe_rollout_runs_td.h, instantiated in qe_inst_runs_td.hip) and evaluated greedily by k_evaluate_runs
 // (qe_rollout_runs.h, instantiated in qe_inst_runs.hip), plus the compaction of the per-run episode-log segments and
-// the per-run draw counters.
+// the per-run draw counters.  With the double estimator on (qe_population_set_double) a second table B of the same
+// shape stands beside the engine's table A: k_double_rollout trains both and k_double_evaluate acts on their sum
+// (qe_rollout_double.h, instantiated in qe_inst_runs_double.hip).
 #include "qe_host.h"
 
 namespace {
@@ -190,6 +192,18 @@ int pending_reserve(qe_engine* e) {
     return QE_OK;
 }
 
+// The double estimator's table entry points: the qe_table_* call `f` with table B standing in for the engine's table.
+template <class F>
+int on_table_b(qe_engine* e, F f) {
+    if (int rc = need_population(e)) return rc;
+    if (!e->pop.table_b) return qe_fail(QE_ERR_INVALID, "the double estimator is off (qe_population_set_double)");
+    void* const a = e->q;
+    e->q = e->pop.table_b;
+    const int rc = f();
+    e->q = a;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -293,7 +307,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
     if (P.rule == QE_RULE_SARSA)
         if (int rc = pending_reserve(e)) return rc;
     CallLog L;
-    int64_t launches = 0, variant = QE_VARIANT_RUNS;
+    int64_t launches = 0, variant = P.table_b ? QE_VARIANT_RUNS_DOUBLE : QE_VARIANT_RUNS;
     HIP_TRY(hipEventRecord(P.ev0, e->stream));
     for (long long t = 0; t < steps; t += per_launch) {
         const long long k = std::min<long long>(per_launch, steps - t);
@@ -311,6 +325,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.mode = mode; c.nan_select = nan_select;
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
+                if (P.table_b) return launch_double_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, (T*)P.table_b);
                 if (P.rule != QE_RULE_Q_LEARNING)
                     return launch_runs_td<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p);
                 return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
@@ -385,7 +400,7 @@ int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t
     const int nan_select = e->A > 10 ? 1 : 0;
     const EnvCtx ev = make_envctx(e, env);
     CallLog L;
-    int64_t launches = 0, variant = QE_VARIANT_RUNS_EVAL;
+    int64_t launches = 0, variant = P.table_b ? QE_VARIANT_RUNS_DOUBLE_EVAL : QE_VARIANT_RUNS_EVAL;
     bool all_done = false;
     HIP_TRY(hipEventRecord(P.ev0, e->stream));
     for (long long t = 0; t < steps && !all_done; t += per_launch) {
@@ -403,6 +418,10 @@ int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t
                 c.nan_select = nan_select;
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
+                if (P.table_b)
+                    return launch_double_evaluate<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, episodes,
+                                                          episodes ? P.used.p : nullptr, episodes ? P.done.p : nullptr,
+                                                          (const T*)P.table_b);
                 return launch_evaluate_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, episodes,
                                                     episodes ? P.used.p : nullptr, episodes ? P.done.p : nullptr);
             };
@@ -480,6 +499,8 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
     if (int rc = need_population(e)) return rc;
     if (rule != QE_RULE_Q_LEARNING && rule != QE_RULE_SARSA && rule != QE_RULE_EXPECTED_SARSA)
         return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
+    if (e->pop.table_b && rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (qe_population_set_double)");
     e->pop.rule = rule;
     return QE_OK;
 }
@@ -487,6 +508,63 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
 int qe_population_update_rule(qe_engine* e) {
     if (int rc = need_population(e)) return rc;
     return e->pop.rule;
+}
+
+int qe_population_set_double(qe_engine* e, int32_t on) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (P.rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", P.rule);
+    HIP_TRY(hipSetDevice(e->device));
+    if (!on) {
+        if (P.table_b) {
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            (void)hipFree(P.table_b);
+            P.table_b = nullptr;
+        }
+        return QE_OK;
+    }
+    if (P.table_b) return QE_OK;
+    // table B: zeros, and -inf in the padding columns, exactly as qe_create leaves table A
+    const size_t bytes = (size_t)e->S * e->ld * e->esize();
+    void* b = nullptr;
+    hipError_t err = hipMalloc(&b, bytes);
+    if (err == hipSuccess) err = hipMemsetAsync(b, 0, bytes, e->stream);
+    if (err == hipSuccess && e->ld > e->A) {
+        const int64_t cells = e->S * (int64_t)(e->ld - e->A);
+        if (e->dtype == QE_F32)
+            hipLaunchKernelGGL(k_pad_fill<float>, dim3(grid_for(cells, 256)), dim3(256), 0, e->stream, (float*)b, e->S, e->A, e->ld);
+        else
+            hipLaunchKernelGGL(k_pad_fill<double>, dim3(grid_for(cells, 256)), dim3(256), 0, e->stream, (double*)b, e->S, e->A, e->ld);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    if (err != hipSuccess) {
+        if (b) (void)hipFree(b);
+        return qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "allocation of the second table failed: %s",
+                       hipGetErrorString(err));
+    }
+    P.table_b = b;
+    return QE_OK;
+}
+
+int qe_population_double(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    if (e->pop.rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", e->pop.rule);
+    return e->pop.table_b ? 1 : 0;
+}
+
+int qe_population_table_b_upload(qe_engine* e, const void* host, int32_t host_dtype) {
+    return on_table_b(e, [&] { return qe_table_upload(e, host, host_dtype); });
+}
+
+int qe_population_table_b_download(qe_engine* e, void* host, int32_t host_dtype) {
+    return on_table_b(e, [&] { return qe_table_download(e, host, host_dtype); });
+}
+
+int qe_population_table_b_download_rows(qe_engine* e, void* host, int64_t first_row, int64_t rows) {
+    return on_table_b(e, [&] { return qe_table_download_rows(e, host, first_row, rows); });
 }
 
 int qe_population_pending_actions(qe_engine* e, int32_t* out) {

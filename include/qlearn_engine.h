@@ -93,7 +93,9 @@ typedef struct qe_rollout_stats {
                                 path 6: population (qe_population_rollout), path 7: population greedy evaluation
                                 (qe_population_evaluate), both with the same NV and masked bits; path 8: population with
                                 an on-policy update rule (SARSA / Expected SARSA): those NV and masked bits, and the rule
-                                (qe_update_rule) in bits 4-5 */
+                                (qe_update_rule) in bits 4-5; path 9: population with the double estimator (Double
+                                Q-learning, qe_population_set_double) and path 10: its greedy evaluation, both with
+                                the NV and masked bits of path 6 */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -334,7 +336,20 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         already chosen for each run's next step (`runs` entries, -1 = none: the run picks at its next
  *                         step).  The rollout leaves it behind; set it (NULL: none for every run) when the environment
  *                         state is restored or reset.  Entries outside [-1, action_size) -> QE_ERR_INVALID.  Other rules
- *                         neither read nor write it. */
+ *                         neither read nor write it.
+ *   qe_population_set_double / qe_population_double  the double estimator (Double Q-learning, van Hasselt 2010): every run
+ *                         owns two tables, A (the engine's table: every qe_table_* entry point keeps seeing A only) and B
+ *                         (a second allocation of the same shape and row stride, zero when the switch is turned on, freed
+ *                         when it is turned off).  A run picks from the sum row T(A[s, .] + B[s, .]); bit 31 of the unused
+ *                         fourth word of the step's policy draws chooses the table X that is updated (0: A, 1: B), and
+ *                         X[s, a] bootstraps from Y[s', argmax X[s', valid]], Y the other table (first index of the
+ *                         maximum, a NaN counting as the maximum).  Greedy evaluation picks from the sum row.  An
+ *                         orthogonal switch, not an update rule: it exists for Q-learning only.  Not a population engine
+ *                         -> QE_ERR_INVALID; the update rule is not Q-learning -> QE_ERR_UNSUPPORTED, and so is
+ *                         qe_population_set_update_rule to another rule while the switch is on.  qe_population_double
+ *                         returns 1 / 0 (or a negative qe_status).
+ *   qe_population_table_b_upload / _download / _download_rows  qe_table_upload / qe_table_download /
+ *                         qe_table_download_rows on table B; QE_ERR_INVALID while the switch is off. */
 enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
 typedef struct qe_run_schedule {
@@ -361,6 +376,11 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule);
 int qe_population_update_rule(qe_engine* e);
 int qe_population_pending_actions(qe_engine* e, int32_t* out);
 int qe_population_set_pending_actions(qe_engine* e, const int32_t* in);
+int qe_population_set_double(qe_engine* e, int32_t on);
+int qe_population_double(qe_engine* e);
+int qe_population_table_b_upload(qe_engine* e, const void* host, int32_t host_dtype);
+int qe_population_table_b_download(qe_engine* e, void* host, int32_t host_dtype);
+int qe_population_table_b_download_rows(qe_engine* e, void* host, int64_t first_row, int64_t rows);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

@@ -2,7 +2,7 @@
 rollout on the same environment, measured in the same process.
 
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
-                                    [--rule q_learning|sarsa|expected_sarsa] [--actions A]
+                                    [--rule q_learning|sarsa|expected_sarsa] [--double] [--actions A]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
@@ -12,6 +12,9 @@ run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/populati
 
 --rule trains with that update rule (k_rollout_runs_td for sarsa / expected_sarsa; the standalone baseline is always
 the Q-learning one-agent rollout) and writes DIR/population_rate_<rule>.json for a rule other than q_learning.
+--double trains (or, with --evaluate, evaluates) a Double Q-learning population (double_q=True: k_double_rollout /
+k_double_evaluate, two tables per run) against the same single-table standalone baseline and writes
+DIR/population_rate_double.json (DIR/population_eval_rate_double.json).
 --actions A adds a HashTabularEnv of 1e4 states x A actions at M = 4096 (the wide-row builds: A = 64 is NV = 16).
 
 --evaluate measures greedy evaluation instead (QLearningPopulation.evaluate_steps, k_evaluate_runs) on the same
@@ -68,9 +71,11 @@ def schedules():
     return ExponentialSchedule(0.1, 1e-3, 0.9995), ExponentialSchedule(1.0, 0.05, 0.9995)
 
 
-def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning"):
+def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False):
     lr, eps = schedules()
     kw = {} if rule == "q_learning" else {"update_rule": rule}
+    if double_q:
+        kw["double_q"] = True
     pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
@@ -82,9 +87,9 @@ def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning"):
             "episodes": int(res.episode_counts.sum()), "kernel_variant": int(pop.last_stats["kernel_variant"])}
 
 
-def population_eval_rate(make_env, M, S, A, steps, dtype, log):
+def population_eval_rate(make_env, M, S, A, steps, dtype, log, double_q=False):
     lr, eps = schedules()
-    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype)
+    pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **({"double_q": True} if double_q else {}))
     pop.run_steps(200, make_env(M), log=False)  # tables that are not all zero
     env = make_env(M)
     pop.evaluate_steps(env, min(200, steps), log=log)  # warm-up: code objects, allocations
@@ -132,10 +137,13 @@ def main() -> None:
     ap.add_argument("--evaluate", action="store_true", help="greedy evaluation (evaluate_steps) instead of training")
     ap.add_argument("--rule", choices=["q_learning", "sarsa", "expected_sarsa"], default="q_learning",
                     help="update rule of the trained population (not with --evaluate: evaluation does not depend on it)")
+    ap.add_argument("--double", action="store_true", help="Double Q-learning: two tables per run (q_learning only)")
     ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
     if args.evaluate and args.rule != "q_learning":
         ap.error("--rule applies to training runs only")
+    if args.double and args.rule != "q_learning":
+        ap.error("--double is Double Q-learning: it goes with --rule q_learning")
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
     P, isd = frozen_lake_8x8_slippery()
@@ -161,11 +169,11 @@ def main() -> None:
         if name not in base_cache:
             base_cache[name] = (standalone_eval_rate if args.evaluate else standalone_rate)(make_env, S, A, min(k, 5000), dtype)
         if args.evaluate:
-            pop = population_eval_rate(make_env, M, S, A, k, dtype, log)
+            pop = population_eval_rate(make_env, M, S, A, k, dtype, log, args.double)
         else:
-            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule)
+            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double)
         base = base_cache[name]
-        line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
+        line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, **({"double": True} if args.double else {}), "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
                 "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
         lines.append(line)
         print(f"{name:14s} M={M:6d} log={int(log)} {pop['env_steps_per_s'] / 1e6:10.1f} M env-steps/s "
@@ -175,6 +183,8 @@ def main() -> None:
     name = "population_eval_rate.json" if args.evaluate else "population_rate.json"
     if args.rule != "q_learning":
         name = f"population_rate_{args.rule}.json"
+    if args.double:
+        name = name.replace(".json", "_double.json")
     (args.out / name).write_text(json.dumps(lines, indent=1))
 
 
