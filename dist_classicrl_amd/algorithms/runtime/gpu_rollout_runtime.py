@@ -387,6 +387,9 @@ class GpuRolloutQLearning(BaseRuntime):
         start = self.algorithm.step_counter
         history, used, chunk = [], 0, 64
         while len(history) < episodes:
+            # the launch may run past the step that reaches the target; the reference stops there, and so must the
+            # environment it leaves behind (observations, internal state, running returns)
+            before = (*env.observe(), env.aux())
             rets, at = self._rollout(env, chunk, learn=False)
             need = episodes - len(history)
             if rets.size >= need:
@@ -395,6 +398,10 @@ class GpuRolloutQLearning(BaseRuntime):
                 last_step = at[need - 1]
                 keep = int(np.searchsorted(at, last_step, side="right"))
                 history.extend(rets[:keep])
+                if int(last_step) + 1 < chunk:  # the same steps again from the state before the launch, and no further
+                    env.restore(*before)
+                    self.algorithm.step_counter = start + used
+                    self._rollout(env, int(last_step) + 1, learn=False)
                 used += int(last_step) + 1
                 break
             history.extend(rets)

@@ -273,3 +273,47 @@ class TicTacToeVecEnv(_VecEnvBase):
                 self._begin_episode(i, h1[i], h2[i])
         truncated = np.zeros(n, dtype=bool)
         return self._obs(), rewards, terminated, truncated, [{}] * n
+
+
+def clock_env(env, clock):
+    """Environments that draw per (agent, vector step) keep the index of the step in ``step_index`` and count it up
+    themselves, which is right for one uninterrupted rollout from step 0.  The engine's environments draw at the
+    algorithm's step counter instead, which also counts the steps of other environments (``train``: validation between
+    training chunks) and may start anywhere.  ``clock_env`` makes ``env.step`` read the index from ``clock()`` -- the
+    index of the vector step being executed -- and returns ``env``; environments without such draws are left alone."""
+    if hasattr(env, "step_index"):
+        inner = env.step
+
+        def step(actions):
+            env.step_index = clock()
+            return inner(actions)
+
+        env.step = step
+    return env
+
+
+def env_aux(env):
+    """The environment-internal per-agent state as the engine keeps it (``DeviceVecEnv.aux()``, csrc/qe_envs.h): the
+    episode counter (hash), the step within the episode (bandit), the board marks and the agent's mark (TicTacToe:
+    mark-1 cells | mark-2 cells << 9 | agent plays mark 2 << 18), 0 elsewhere."""
+    if isinstance(env, HashTabularEnv):
+        return env.episode.astype(np.uint32)
+    if isinstance(env, RiggedBanditVecEnv):
+        return env.t.astype(np.uint32)
+    if isinstance(env, TicTacToeVecEnv):
+        return (env.m1 | (env.m2 << 9) | ((env.agent_mark == 2).astype(np.int64) << 18)).astype(np.uint32)
+    return np.zeros(env.num_agents, dtype=np.uint32)
+
+
+def make_env(spec, agent_offset=0, seed=1):
+    """An environment from the spec tuples of the golden case tables: ("hash", agents, S, A, masked[, p_term_256]),
+    ("grid", agents, side), ("ttt", agents), ("bandit", agents, episode_len)."""
+    kind = spec[0]
+    if kind == "hash":
+        extra = {"p_term_256": spec[5]} if len(spec) > 5 else {}
+        return HashTabularEnv(spec[1], spec[2], spec[3], seed=seed, masked=spec[4], agent_offset=agent_offset, **extra)
+    if kind == "grid":
+        return GridLakeEnv(spec[1], side=spec[2], seed=seed)
+    if kind == "ttt":
+        return TicTacToeVecEnv(spec[1], seed=seed, agent_offset=agent_offset)
+    return RiggedBanditVecEnv(spec[1], episode_len=spec[2])

@@ -341,6 +341,7 @@ class OracleRuntime:
                 if te[i] or tr[i]:
                     history.append(acc[i])
                     acc[i] = 0
+        self.eval_running_returns = acc  # (a local of the reference's method; the engine keeps it with the environment)
         return sum(history), history
 
     def evaluate_episodes(self, env, episodes):
@@ -358,4 +359,24 @@ class OracleRuntime:
                     done += 1
                     history.append(acc[i])
                     acc[i] = 0
+        self.eval_running_returns = acc
         return sum(history), history
+
+    def train(self, env, steps, val_env, val_every_n_steps, val_steps=None, val_episodes=None, curr_state_dict=None):
+        # base_runtime.py:99-182 -- chunks of ``val_every_n_steps`` (the last one shorter), a validation after every
+        # chunk.  ``curr_state_dict`` is handed to every chunk unchanged (:156-161: the dict ``run_steps`` returns is
+        # never fed back), so with the default None every chunk starts from ``env.reset()``; the validation total is
+        # what ``evaluate_*`` returns first.
+        assert (val_steps is None) ^ (val_episodes is None), "Exactly one of val_steps or val_episodes must be specified."
+        reward_history, val_reward_history, state_dict = [], [], None
+        for step in range(0, steps, val_every_n_steps):
+            _, episode_rewards, env, state_dict = self.run_steps(
+                min(val_every_n_steps, steps - step), env, curr_state_dict
+            )
+            reward_history.extend(episode_rewards)
+            if val_steps is not None:
+                total, _ = self.evaluate_steps(val_env, val_steps)
+            else:
+                total, _ = self.evaluate_episodes(val_env, val_episodes)
+            val_reward_history.append(total)
+        return reward_history, val_reward_history, env, state_dict

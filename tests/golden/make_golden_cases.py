@@ -109,3 +109,101 @@ NAN_TRACE_CASES = [
     ("nan_lean_n128", ("hash", 128, 2000, 16, False), [20, 20, 20, 20], "f4", "const", "learn", 1, 4),
     ("nan_ttt_n128", ("ttt", 128), [10, 10], "f4", "const", "learn", 300, 3),
 ]
+
+# ---- greedy evaluation and train() (make_golden_eval.py) ---------------------------------------------------------------
+# Shared by the generator (needs the reference) and by tests/test_oracle_eval_golden.py / tests/test_gpu_eval_parity.py,
+# which import these tables and constructions from here: there is no second copy to keep in step.
+import numpy as np  # noqa: E402
+
+
+def tie_rich_table(seed, S, A, dt):
+    """``make_golden.py:_tie_rich_table`` on ``default_rng(seed)``: Q-values from a tiny value set so that arg-max ties
+    are common; some all-zero rows."""
+    rng = np.random.default_rng(seed)
+    q = rng.choice(np.array([0.0, 0.25, 0.5, 1.0, -0.5]), size=(S, A)).astype(dt)
+    q[rng.random(S) < 0.2] = 0
+    return q
+
+
+def nan_table(S, A, dt, cells, seed):
+    """``make_golden_r3.py:nan_table``: a random table with `cells` NaN entries."""
+    rng = np.random.default_rng(seed)
+    q = rng.standard_normal((S, A)).astype(dt)
+    if cells:
+        q.ravel()[rng.choice(S * A, size=cells, replace=False)] = np.nan
+    return q
+
+
+def eval_table(table, S, A, dt, valid=None):
+    """The initial table of an evaluation case.  ``table`` is ("tie", seed), ("zero",), ("nan", cells, seed),
+    ("nan_rows", cells, seed, every): as "nan" with every `every`-th row NaN throughout, or ("nan_masked", seed): a
+    tie-rich table with NaN in half of the cells whose action the environment's mask of that state clears (`valid`:
+    bool[S, A], the mask of every state)."""
+    kind = table[0]
+    if kind == "tie":
+        return tie_rich_table(table[1], S, A, dt)
+    if kind == "zero":
+        return np.zeros((S, A), dtype=dt)
+    if kind == "nan":
+        return nan_table(S, A, dt, table[1], table[2])
+    if kind == "nan_rows":
+        q = nan_table(S, A, dt, table[1], table[2])
+        q[::table[3]] = np.nan
+        return q
+    assert kind == "nan_masked" and valid is not None
+    q = tie_rich_table(table[1], S, A, dt)
+    q[~valid & (np.random.default_rng(table[1] + 1).random((S, A)) < 0.5)] = np.nan
+    return q
+
+
+def table_print(q):
+    """Fingerprint of a table's bit patterns (two uint64 words): the goldens store it next to results computed from a
+    table that the tests rebuild from its seed, so that a construction that drifts is noticed as such."""
+    bits = np.ascontiguousarray(q).view(np.uint32 if q.dtype.itemsize == 4 else np.uint64).ravel().astype(np.uint64)
+    weights = np.arange(1, bits.size + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    return np.array([np.bitwise_xor.reduce(bits * weights), np.add.reduce(bits ^ weights)], dtype=np.uint64)
+
+
+EVAL_SEED = 0  # policy draw seed of every golden evaluation / train case
+
+EVAL_CASES = [
+    # (name, env spec (oracle.envs.make_env), dtype, table, start step, vector steps of the steps-mode call (steps = that x agents + extra),
+    #  extra, episode target (None: steps mode only), raises)
+    # -- the shapes: both modes each; the smallest that reach each branch.  (A sixth spec entry is the termination rate in
+    #    256ths, default 13: lowered where many agents would otherwise fill the file with episode returns.)
+    # (one action: the walk is a fixed cycle, which at the default termination rate holds no terminal state; 64/256 here)
+    ("hash_n1_a1", ("hash", 1, 50, 1, False, 64), "f4", ("tie", 11), 3, 700, 0, 70, False),       # single action, single agent
+    ("hash_n63_a4_f8", ("hash", 63, 200, 4, False), "f8", ("tie", 12), 0, 40, 0, 393, False),     # L = 1, partial wavefront
+    ("hash_n65_a5", ("hash", 65, 200, 5, False), "f4", ("tie", 13), 17, 40, 0, 200, False),       # L = 2, padded row
+    ("hash_masked_n100_a9_f8", ("hash", 100, 300, 9, True, 6), "f8", ("tie", 14), 5, 40, 0, 740, False),  # L = 4, list
+    ("hash_n128_a10", ("hash", 128, 300, 10, False, 6), "f4", ("tie", 15), 0, 40, 0, 1121, False),   # last list-variant width
+    ("hash_n128_a11", ("hash", 128, 300, 11, False, 6), "f4", ("tie", 16), 9, 40, 0, 608, False),   # first NumPy-variant width
+    ("hash_masked_n257_a16", ("hash", 257, 500, 16, True, 3), "f4", ("tie", 17), 0, 40, 0, 706, False),  # agents % groups
+    ("hash_n300_a33_f8", ("hash", 300, 400, 33, False, 3), "f8", ("tie", 18), 100, 40, 0, 733, False),   # L = 16, padded
+    ("hash_masked_n96_a64", ("hash", 96, 300, 64, True), "f4", ("tie", 19), 0, 40, 0, 854, False),     # the c5 width
+    ("hash_n70_a100", ("hash", 70, 100, 100, False), "f4", ("tie", 20), 1000, 40, 0, 726, False),      # L = 32
+    ("hash_masked_n40_a256_f8", ("hash", 40, 60, 256, True), "f8", ("tie", 21), 0, 60, 0, 465, False),  # L = 64
+    ("hash_n1000_a16_zero", ("hash", 1000, 64, 16, False, 4), "f4", ("zero",), 0, 30, 0, 2633, False),  # every pick a full tie
+    ("ttt_n90", ("ttt", 90), "f4", ("tie", 22), 0, 40, 0, 4689, False),                   # masked list variant, env state
+    ("grid4_n16_f8", ("grid", 16, 4), "f8", ("tie", 43), 0, 200, 0, None, False),         # steps mode only
+    ("bandit_n130", ("bandit", 130, 7), "f4", ("tie", 24), 0, 40, 0, 130 * 27 + 1, False),  # all finish in one step: log order
+    # -- the step word crosses 2**32 during the call (k_eval hands step >> 32 to Philox)
+    ("hash_n128_a16_step32", ("hash", 128, 300, 16, False, 6), "f4", ("tie", 25), 2**32 - 20, 40, 0, 751, False),
+    # -- steps = 30 * n + 1: ceil(steps / n) = 31 vector steps
+    ("hash_n96_a8_ceil", ("hash", 96, 300, 8, False), "f4", ("tie", 26), 0, 30, 1, None, False),
+    # -- NaN tables
+    # (steps mode only: without ties the greedy walks of a random table end in cycles that hold no terminal state)
+    ("nan_list_a8", ("hash", 64, 300, 8, False), "f4", ("nan", 300, 31), 0, 40, 0, None, False),    # list variant steps over NaN
+    ("nan_allrow_a8", ("hash", 64, 300, 8, False), "f4", ("nan_rows", 300, 32, 5), 0, 40, 0, 620, True),  # a row without candidate
+    ("nan_max_a16", ("hash", 64, 300, 16, False), "f4", ("nan", 200, 33), 0, 40, 0, 620, True),     # np.max propagates
+    ("nan_masked_out_a16", ("hash", 64, 300, 16, True), "f4", ("nan_masked", 34), 0, 40, 0, 548, False),  # NaN never valid
+]
+
+TRAIN_CASES = [
+    # (name, env spec, validation agents, dtype, schedule kind, learn fn, steps, val_every_n_steps, ("steps" | "episodes", count))
+    ("hash_n96_a8_bench", ("hash", 96, 500, 8, False), 40, "f4", "bench", "learn", 50, 16, ("steps", 40 * 30)),      # fused short calls
+    ("hash_masked_n64_a9_f8", ("hash", 64, 300, 9, True), 100, "f8", "const", "learn", 45, 20, ("episodes", 150)),  # not fused
+    ("ttt_n64", ("ttt", 64), 24, "f4", "const", "learn", 40, 15, ("episodes", 60)),
+    ("bandit_n4_f8_kat", ("bandit", 4, 5), 6, "f8", "kat", "learn", 35, 12, ("steps", 6 * 12)),
+    ("hash_n128_a16_vec", ("hash", 128, 64, 16, False), 200, "f8", "const", "learn_vec", 35, 12, ("steps", 200 * 25)),
+]

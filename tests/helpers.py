@@ -6,12 +6,16 @@ from pathlib import Path
 
 import numpy as np
 
-from oracle.envs import GridLakeEnv, HashTabularEnv, RiggedBanditVecEnv, TicTacToeVecEnv
+from oracle.draws import InjectedDraws
+from oracle.envs import (GridLakeEnv, HashTabularEnv, RiggedBanditVecEnv, TicTacToeVecEnv, clock_env, env_aux,
+                         make_env)
 from oracle.qlearn_oracle import OracleQLearning, OracleRuntime, OracleSchedule
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
-# must mirror tests/golden/make_golden.py:TRACE_CASES (name -> env spec, steps, dtype, schedules, learn)
+# must mirror tests/golden/make_golden.py:TRACE_CASES (name -> env spec, steps, dtype, schedules, learn).  (The tables of
+# the evaluation / train goldens, EVAL_CASES and TRAIN_CASES, have no mirror: generator and tests both import them from
+# tests/golden/make_golden_cases.py.)
 TRACE_CASES = {
     "c1_grid_n1": (("grid", 1, 10), 80, "f8", "bench", "iter"),
     "grid4_n1": (("grid", 1, 4), 300, "f8", "bench", "iter"),
@@ -213,3 +217,104 @@ def shares_a_cell_within_a_step(cells, n):
     """True if some step's `n` records name one cell more than once (the case is not contention-free)."""
     by_step = np.sort(np.asarray(cells).reshape(-1, n), axis=1)
     return bool((by_step[:, 1:] == by_step[:, :-1]).any())
+
+
+# ------------------------------------------------------------------------------- greedy evaluation and train()
+def _obs_of(env):
+    return np.asarray(env.obs if hasattr(env, "obs") else env._obs()["observation"], dtype=np.int32)
+
+
+def masks_of_every_state(spec):
+    """bool[S, A] action masks of a masked hash spec as evaluation sees them (reset(seed=42) re-seeds the masks)."""
+    env = make_env(spec)
+    if not env.masked:
+        return None
+    env.reset(seed=42)
+    return env.action_masks(np.arange(env.state_size, dtype=np.int32)).astype(bool)
+
+
+ORACLE_MAX_CALLS = 5000  # selections per oracle runtime: a greedy policy that never ends an episode fails, it does not hang
+
+
+def _oracle_runtime(env_like, dt, sched, learn_mode, seed, agent_offset, q0=None, start=0, max_calls=ORACLE_MAX_CALLS):
+    algo = OracleQLearning(env_like.state_size, env_like.action_size, 0.99, seed=seed, dtype=np.dtype(dt))
+    if agent_offset:
+        algo._rng = algo._np_rng = InjectedDraws(seed, np.arange(agent_offset, agent_offset + 4096, dtype=np.uint32))
+    if q0 is not None:
+        algo.q_table = np.array(q0, dtype=np.dtype(dt))
+    lr_p, eps_p = schedule_params(sched)
+    rt = OracleRuntime(algo, OracleSchedule(*lr_p), OracleSchedule(*eps_p), learn_mode=learn_mode)
+    rt.step_counter = int(start)
+    rt.calls = 0
+    inner = algo.choose_actions
+
+    def choose_actions(*args, **kw):
+        # counts the calls; an agent without a candidate (-1 from a list variant, q_learning_optimal.py:302, :348) is
+        # reported as the engine reports it on every path: IndexError (include/qlearn_engine.h)
+        rt.calls += 1
+        if rt.calls > max_calls:
+            msg = f"more than {max_calls} selections: the evaluated policy does not end episodes (choose another case)"
+            raise RuntimeError(msg)
+        actions = inner(*args, **kw)
+        if (np.asarray(actions) < 0).any():
+            msg = "no selectable action (-1 from a list variant)"
+            raise IndexError(msg)
+        return actions
+
+    algo.choose_actions = choose_actions
+    return rt
+
+
+def run_oracle_eval(spec, dt, q0, start, mode, count, seed=0, agent_offset=0, rt=None, max_calls=ORACLE_MAX_CALLS):
+    """``OracleRuntime.evaluate_steps`` / ``evaluate_episodes`` (`mode`) on a fresh environment of `spec`, from step
+    index `start` on table `q0`; with `rt` on that runtime as it stands (its table and counter).  Returns total,
+    history, the environment's observations and internal state after the call, the runtime's step counter, the number
+    of ``choose_actions`` calls and whether IndexError was raised."""
+    env = make_env(spec, agent_offset=agent_offset)
+    if rt is None:
+        rt = _oracle_runtime(env, dt, "const", "iter", seed, agent_offset, q0, start, max_calls)
+    clock_env(env, lambda: rt.step_counter)
+    calls0, raised, total, history = rt.calls, False, 0.0, []
+    try:
+        with np.errstate(all="ignore"):
+            total, history = getattr(rt, "evaluate_" + mode)(env, count)
+    except IndexError:
+        raised = True
+    return {"total": total, "history": np.array(history, dtype=np.float32), "obs": _obs_of(env), "aux": env_aux(env),
+            "step_counter": rt.step_counter, "calls": rt.calls - calls0, "raised": raised, "rt": rt,
+            "acc": None if raised else rt.eval_running_returns}
+
+
+def run_oracle_train(spec, val_n, dt, sched, learn_mode, steps, every, val, seed=0, agent_offset=0):
+    """``OracleRuntime.train`` on fresh training / validation environments of `spec` (`val_n` validation agents);
+    `val` is ("steps" | "episodes", count)."""
+    env = make_env(spec, agent_offset=agent_offset)
+    val_env = make_env((spec[0], val_n) + tuple(spec[2:]), agent_offset=agent_offset)
+    rt = _oracle_runtime(env, dt, sched, learn_mode, seed, agent_offset)
+    clock_env(env, lambda: rt.step_counter)
+    clock_env(val_env, lambda: rt.step_counter)
+    kw = {"val_steps": val[1]} if val[0] == "steps" else {"val_episodes": val[1]}
+    rewards, val_rewards, _, sd = rt.train(env, steps, val_env, every, **kw)
+    states = sd["states"]
+    return {"reward_history": np.array(rewards, dtype=np.float32), "val_reward_history": np.array(val_rewards, dtype=np.float64),
+            "q": rt.algorithm.q_table, "final_sched": np.array([rt.lr_schedule.get_value(), rt.exploration_rate_schedule.get_value()]),
+            "obs": np.asarray(states["observation"] if isinstance(states, dict) else states, dtype=np.int32),
+            "agent_rewards": np.asarray(sd["rewards"], dtype=np.float32), "aux": env_aux(env), "val_obs": _obs_of(val_env),
+            "val_aux": env_aux(val_env), "step_counter": rt.step_counter, "calls": rt.calls}
+
+
+def golden_eval_record(g, name, mode):
+    meta = g[f"eval/{name}/{mode}/meta"]
+    state = g[f"eval/{name}/{mode}/state"]
+    return {"print": meta[:2], "raised": bool(meta[2]), "no_candidate": bool(meta[3]), "start": int(meta[4]),
+            "calls": int(meta[5]), "total": float(meta[6:7].view(np.float64)[0]), "history": g[f"eval/{name}/{mode}/history"],
+            "obs": state[0].view(np.int32), "aux": state[1]}
+
+
+def golden_train_record(g, name, shape, dt):
+    p = f"train/{name}/"
+    meta, state, val_state = g[p + "meta"], g[p + "state"], g[p + "val_state"]
+    return {"reward_history": g[p + "reward_history"], "val_reward_history": g[p + "val_reward_history"],
+            "q": dense_from_sparse(g[p + "q_idx"], g[p + "q_val"], shape, np.dtype(dt)), "final_sched": meta[:2],
+            "calls": int(meta[2]), "obs": state[0].view(np.int32), "aux": state[1], "agent_rewards": state[2].view(np.float32),
+            "val_obs": val_state[0].view(np.int32), "val_aux": val_state[1]}
