@@ -206,6 +206,8 @@ PROTOTYPES = {
     "qe_population_table_b_download": (C.c_int, [_P, _P, C.c_int32]),
     "qe_population_table_b_download_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "qe_debug_set_turn_epoch": (C.c_int, [_P, C.c_uint64]),
+    "qe_debug_turn_epoch": (C.c_uint64, [_P]),
     "qe_replay_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "qe_replay_destroy": (C.c_int, [_P]),
     "qe_replay_push": (C.c_int, [_P, _I64P, _I64P, _F64P, _I64P, _U8P, C.c_int64]),

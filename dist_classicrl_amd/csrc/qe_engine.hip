@@ -259,6 +259,16 @@ void learn_from_launch(qe_engine* e, const RolloutSlot& sl, const Ctrl& fin) {
 // Turnstile path: one 64-byte record per (row, step parity), 128 B per table row, allocated when the path is first
 // taken.  No room for them (a table that fills the device): e->turn_no_memory is set and the call runs the step-wise /
 // wide kernels instead, as for any shape the path does not take -- same results.
+// Tag of step 0 of a call of `steps` steps when the engine's next free tag is `epoch`: `epoch` itself unless the call's
+// tags (epoch .. epoch + steps, and the two the engine keeps in reserve behind them) would reach or cross a multiple of
+// 2^32, or start on one -- then the next multiple of 2^32 plus 1 (`moved`: the records must be cleared first).
+unsigned long long turn_epoch_for_call(unsigned long long epoch, int64_t steps, bool* moved) {
+    const unsigned long long end = epoch + (unsigned long long)steps + 2ull;
+    *moved = (uint32_t)epoch == 0u || (end >> 32) != (epoch >> 32);
+    if (!*moved) return epoch;
+    return ((((uint32_t)epoch == 0u ? epoch : end) >> 32) << 32) + 1ull;
+}
+
 int turn_setup(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps) {
     const size_t recs = (size_t)e->S * 2;
     const bool fresh = e->turn_rows.cap < recs;
@@ -272,9 +282,17 @@ int turn_setup(qe_engine* e, qe_env* env, RolloutSlot& sl, int64_t steps) {
         HIP_TRY(err);
     }
     HIP_TRY(env->turn_next.ensure((size_t)env->N * 4));
-    // the records carry a 32-bit step tag and are never cleared per step: zeroed when allocated and before a tag can repeat
-    if (fresh || ((e->turn_epoch + (unsigned long long)steps + 2ull) >> 31) != (e->turn_epoch >> 31))
+    // The records carry a 32-bit step tag and are never cleared per step.  Tags only grow between two clears of the
+    // array (turn_push2 restarts a record with an atomic max) and tag 0 means "cleared record", so no call may straddle
+    // a multiple of 2^32 and none may issue tag 0: turn_epoch_for_call moves such a call to the next multiple of 2^32
+    // plus 1.  The array is zeroed when allocated, whenever the tags cross 2^31 or are moved, and after
+    // qe_debug_set_turn_epoch.
+    bool moved = false;
+    e->turn_epoch = turn_epoch_for_call(e->turn_epoch, steps, &moved);
+    if (fresh || moved || e->turn_clear ||
+        ((e->turn_epoch + (unsigned long long)steps + 2ull) >> 31) != (e->turn_epoch >> 31))
         HIP_TRY(hipMemsetAsync(e->turn_rows.p, 0, e->turn_rows.cap * sizeof(TurnRow), e->stream));
+    e->turn_clear = false;
     sl.turn_epoch = e->turn_epoch;
     e->turn_epoch += (unsigned long long)steps + 2ull;  // tags of this call: epoch .. epoch + steps
     return QE_OK;
@@ -1561,6 +1579,15 @@ int qe_debug_occupy_cus(qe_engine* e, int32_t blocks, int32_t microseconds) {
     HIP_TRY(hipGetLastError());
     return QE_OK;
 }
+
+int qe_debug_set_turn_epoch(qe_engine* e, uint64_t value) {
+    if (!e) return qe_fail(QE_ERR_INVALID, "engine is NULL");
+    if (e->slots[0].busy || e->slots[1].busy) return qe_fail(QE_ERR_INVALID, "a rollout is in flight");
+    e->turn_epoch = value;
+    e->turn_clear = true;  // (the records may hold later tags than `value`: the next turnstile call zeroes them first)
+    return QE_OK;
+}
+uint64_t qe_debug_turn_epoch(qe_engine* e) { return e ? e->turn_epoch : 0; }
 
 // ---- experience replay ring ---------------------------------------------------------------------
 int qe_replay_create(qe_replay** out, int32_t device, int64_t capacity) {

@@ -207,7 +207,10 @@ struct qe_engine {
     uint32_t agent_offset = 0;
     int num_cus = 64;
     int opt_path = 0;  // QE_OPT_ROLLOUT_PATH
-    unsigned long long turn_epoch = 1;  // turnstile path: record tag of the next call's step 0 (0 = a cleared record)
+    // turnstile path: record tag of the next call's step 0.  The low 32 bits are the tag; 0 = a cleared record, so a
+    // call never starts on, reaches or crosses a multiple of 2^32 (turn_setup moves it past and clears the records)
+    unsigned long long turn_epoch = 1;
+    bool turn_clear = false;            // qe_debug_set_turn_epoch: zero the records before the next turnstile call
     DevBuf<TurnRow> turn_rows;          // turnstile path: [S][2] touchers of a row per step parity, allocated on first use
     bool turn_no_memory = false;        // ... that allocation failed: the path is not taken by this engine
     int turn_blocks_per_cu[5] = {0, 0, 0, 0, 0};  // resident workgroups of k_step_turn per CU, by environment kind (0: not yet asked)

@@ -138,7 +138,7 @@ struct Ctx {
     // turnstile path (qe_step_turn.h; nullptr otherwise)
     uint32_t* turn_next;    // [2][N][2] next node of the overflow list an agent is on (per parity and role)
     TurnRow* turn_rows;     // [S][2] touchers of a row per step parity
-    unsigned long long turn_epoch;  // tag of step 0 of this call (tags never repeat in an engine's life)
+    unsigned long long turn_epoch;  // tag of step 0 of this call (32-bit tags grow within a call and never reach 0: turn_setup)
     long long turn_t_off;   // turnstile path: this launch works on step ctrl->t_local + turn_t_off (a launch argument, so
                             // that no launch has to count its finished workgroups to move the step counter)
     Ctrl* ctrl;

@@ -387,6 +387,13 @@ int qe_population_table_b_download_rows(qe_engine* e, void* host, int64_t first_
  * own and returns at once: tests take part of the chip away with it while a rollout runs, the situation of a collective
  * running beside the next chunk of a replica (nothing in the reference to stand in for). */
 int qe_debug_occupy_cus(qe_engine* e, int32_t blocks, int32_t microseconds);
+/* The turnstile path tags its per-row records with a step count that runs through the engine's life (32 bits of it
+ * in the records; a call never starts on, reaches or crosses a multiple of 2^32 -- it is moved to the next multiple
+ * plus 1 and the records are cleared).  qe_debug_set_turn_epoch places that count (the records are cleared before the
+ * next turnstile call), qe_debug_turn_epoch reads the tag the next call would start from before any move: tests reach
+ * the 2^31 / 2^32 edges with them, which otherwise take some 30 hours of turnstile steps. */
+int qe_debug_set_turn_epoch(qe_engine* e, uint64_t value);
+uint64_t qe_debug_turn_epoch(qe_engine* e);
 
 /* ---- experience replay (algorithms/buffers/experience_replay.py:13-120; WIP and unused upstream) --
  * Ring buffer of (state, action, reward, next_state, done) in HBM.  Index SELECTION stays with the

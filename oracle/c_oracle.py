@@ -44,11 +44,14 @@ class CHashRollout:
     """State of one closed-loop run (table, env, bookkeeping) on the C oracle."""
 
     def __init__(self, n, S, A, *, masked=False, env_seed=1, p_term_256=13, agent_offset=0, seed=0,
-                 gamma=0.99, dtype=np.float32, mode="iter"):
+                 gamma=0.99, dtype=np.float32, mode="iter", q=None):
+        """`q`: the (S, A) table to run on instead of a fresh all-zero one (e.g. a lazily zero mapping of a table too
+        large to hold in memory: the loop touches the rows it visits and nothing else)."""
         self.lib = load()
         self.cfg = Cfg(S, A, n, int(masked), env_seed, p_term_256, agent_offset, seed, gamma,
                        0 if np.dtype(dtype) == np.float32 else 1, 0 if mode == "iter" else 1)
-        self.q = np.zeros((S, A), dtype=dtype)
+        self.q = np.zeros((S, A), dtype=dtype) if q is None else q
+        assert self.q.shape == (S, A) and self.q.dtype == np.dtype(dtype) and self.q.flags.c_contiguous
         self.obs = np.zeros(n, dtype=np.int32)
         self.episode = np.zeros(n, dtype=np.uint32)
         self.acc = np.zeros(n, dtype=np.float32)

@@ -2,6 +2,8 @@
 
 from __future__ import annotations
 
+import mmap
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -217,6 +219,97 @@ def shares_a_cell_within_a_step(cells, n):
     """True if some step's `n` records name one cell more than once (the case is not contention-free)."""
     by_step = np.sort(np.asarray(cells).reshape(-1, n), axis=1)
     return bool((by_step[:, 1:] == by_step[:, :-1]).any())
+
+
+# ------------------------------------------------------------------------------- tables too large for the host
+def lazy_zero_table(S, A, dtype):
+    """An all-zero (S, A) table that costs memory only where it is touched: an anonymous private mapping (zero pages on
+    first touch, 4 KiB each: transparent huge pages are declined, NumPy asks for them on large allocations of its own and
+    one touched row would then cost 2 MiB).  For tables of tens of GiB of which a run visits a few thousand rows: index it
+    by rows only -- no whole-array operation, no copy."""
+    dtype = np.dtype(dtype)
+    noreserve = getattr(mmap, "MAP_NORESERVE", 0x4000 if sys.platform.startswith("linux") else 0)
+    m = mmap.mmap(-1, S * A * dtype.itemsize, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS | noreserve)
+    if hasattr(mmap, "MADV_NOHUGEPAGE"):
+        m.madvise(mmap.MADV_NOHUGEPAGE)
+    return np.frombuffer(m, dtype=dtype).reshape(S, A)
+
+
+def resident_bytes():
+    """Resident set size of this process (Linux)."""
+    with open("/proc/self/statm") as f:
+        return int(f.read().split()[1]) * mmap.PAGESIZE
+
+
+def edge_q0(rows, A, dtype):
+    """q0[row, col] of the large-table tests: a cheap function of (row, col), never zero, different from row to row and
+    exact in float32 (a multiple of 2^-18 in (0, 0.25])."""
+    r = np.asarray(rows, dtype=np.uint64).reshape(-1, 1)
+    c = np.arange(A, dtype=np.uint64).reshape(1, -1)
+    h = (r * np.uint64(0x9E3779B1) + c * np.uint64(0x85EBCA77) + np.uint64(0x2545F491)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    return ((h & np.uint64(0xFFFF)) + np.uint64(1)).astype(np.dtype(dtype)) * np.dtype(dtype).type(2.0**-18)
+
+
+def run_sparse_hash_oracle(n, S, A, steps, dt, mode, eps, lr, *, masked=False, placed=(), step0=0, agent_offset=0, seed=0):
+    """The closed loop of the C oracle on a hash environment whose table is never materialised: every row the run reads
+    or writes starts as ``edge_q0`` of it, every other row as zero -- on a ``lazy_zero_table``.  `placed`: start rows of
+    agents 0, 1, ... instead of the environment's reset; `eps` / `lr`: one value per step.
+
+    The set of rows is the fixed point of "seed the rows found so far, run, collect s and s'".  Whole-run passes reach it
+    one step of depth per pass (a newly seeded row changes the greedy action taken there and with it everything behind),
+    so it is built step by step instead: a step selects from the rows the agents stand on (known and seeded before it
+    runs) and reads their successors; a successor that is new is seeded -- nothing has read or written it yet -- and the
+    step is run again from the saved state.  Then ONE whole run from a fresh table with exactly those rows seeded is the
+    reference, and it must touch no row outside the set (the set has stopped growing).
+
+    Returns the C oracle's run dict plus ``rows`` (ascending), ``q_rows`` (their final content), ``reset_obs``,
+    ``final_obs``, ``agent_rewards`` and ``next_obs`` (s' of every record, in record order)."""
+    from oracle import c_oracle
+
+    dt = np.dtype(dt)
+    eps, lr = np.asarray(eps, dtype=np.float64), np.asarray(lr, dtype=np.float64)
+    placed = np.asarray(placed, dtype=np.int32)
+
+    def fresh(rows):
+        ref = c_oracle.CHashRollout(n, S, A, masked=masked, agent_offset=agent_offset, seed=seed, dtype=dt, mode=mode,
+                                    q=lazy_zero_table(S, A, dt))
+        reset_obs = ref.obs.copy()
+        ref.obs[:placed.size] = placed
+        ref.step = step0
+        if len(rows):
+            ref.q[rows] = edge_q0(rows, A, dt)
+        return ref, reset_obs
+
+    ref, _ = fresh(())
+    seeded = np.unique(ref.obs)
+    ref.q[seeded] = edge_q0(seeded, A, dt)
+    for t in range(steps):
+        state = ref.obs.copy(), ref.episode.copy(), ref.acc.copy()
+        stood_on = np.unique(ref.obs)
+        saved = ref.q[stood_on]  # (fancy indexing: a copy of these rows only -- the only rows step t writes)
+        ref.run(eps[t:t + 1], lr[t:t + 1], log_episodes=False)
+        new = np.setdiff1d(ref.obs, seeded)
+        if new.size:
+            ref.q[stood_on] = saved
+            ref.obs[:], ref.episode[:], ref.acc[:] = state
+            ref.step = step0 + t
+            ref.q[new] = edge_q0(new, A, dt)
+            seeded = np.union1d(seeded, new)
+            ref.run(eps[t:t + 1], lr[t:t + 1], log_episodes=False)
+            assert not np.setdiff1d(ref.obs, seeded).size, "the successors of a step moved when they were seeded"
+    del ref
+    ref, reset_obs = fresh(seeded)
+    first_obs = ref.obs.copy()
+    out = ref.run(eps, lr, trace=True, delta_log=True)
+    s = (out["cells"].astype(np.int64) // A).reshape(steps, n)
+    assert np.array_equal(s[0], first_obs)
+    next_obs = np.concatenate([s[1:], ref.obs[None, :].astype(np.int64)]).reshape(-1)  # obs of step t + 1 IS s' of step t
+    touched = np.union1d(s.reshape(-1), next_obs)
+    assert np.isin(touched, seeded).all(), "not a fixed point: the run from the seeded table touched an unseeded row"
+    out.update(rows=seeded.astype(np.int64), q_rows=ref.q[seeded], reset_obs=reset_obs, final_obs=ref.obs.copy(),
+               agent_rewards=ref.acc.copy(), next_obs=next_obs, touched=touched)
+    return out
 
 
 # ------------------------------------------------------------------------------- greedy evaluation and train()
