@@ -34,6 +34,7 @@ OPT_STAMP_HASH_BITS = 9
 PATH_AUTO, PATH_STEPWISE, PATH_PERSISTENT, PATH_WIDE, PATH_TURNSTILE = 0, 1, 2, 3, 4
 
 RULE_Q_LEARNING, RULE_SARSA, RULE_EXPECTED_SARSA = 0, 1, 2  # qe_update_rule
+N_STEP_MAX = 16  # qe_population_set_n_step
 UPDATE_RULES = {"q_learning": RULE_Q_LEARNING, "sarsa": RULE_SARSA, "expected_sarsa": RULE_EXPECTED_SARSA}
 
 ERR_INVALID, ERR_NO_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INDEX = -1, -2, -3, -4, -5
@@ -43,15 +44,20 @@ def decode_variant(v: int) -> dict:
     """Fields of ``qe_rollout_stats.kernel_variant`` (include/qlearn_engine.h).  ``rule``: the population's update rule
     -- path 8 (``population_td``, kernel ``k_rollout_runs_td``) carries it in bits 4-5, where the persistent path keeps
     ``lean``; every other path learns with Q-learning.  Paths 9 and 10 (``population_double``, kernel ``k_double_rollout``,
-    and ``population_double_eval``, ``k_double_evaluate``) are the population with the double estimator."""
+    and ``population_double_eval``, ``k_double_evaluate``) are the population with the double estimator.  Path 11
+    (``population_nstep``, kernel ``k_nstep_rollout``) is the population with an n-step on-policy rule: the rule in
+    bits 4-5 as path 8, and ``n_step`` in bits 24-28 (1 on every other path)."""
     v = int(v)
-    td = (v & 15) == 8
+    nstep = (v & 15) == 11
+    td = (v & 15) == 8 or nstep
     return {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
-                 7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval"}.get(v & 15, "none"),
+                 7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval",
+                 11: "population_nstep"}.get(v & 15, "none"),
         "rule": {1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td else "q_learning",
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
         "cap512": bool((v >> 9) & 1), "dataflow": bool((v >> 10) & 1), "nv": (v >> 12) & 255, "masked": bool((v >> 20) & 1),
+        "n_step": (v >> 24) & 31 if nstep else 1,
     }
 
 
@@ -205,6 +211,10 @@ PROTOTYPES = {
     "qe_population_table_b_upload": (C.c_int, [_P, _P, C.c_int32]),
     "qe_population_table_b_download": (C.c_int, [_P, _P, C.c_int32]),
     "qe_population_table_b_download_rows": (C.c_int, [_P, _P, C.c_int64, C.c_int64]),
+    "qe_population_set_n_step": (C.c_int, [_P, C.c_int32]),
+    "qe_population_n_step": (C.c_int, [_P]),
+    "qe_population_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P]),
+    "qe_population_set_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_debug_set_turn_epoch": (C.c_int, [_P, C.c_uint64]),
     "qe_debug_turn_epoch": (C.c_uint64, [_P]),

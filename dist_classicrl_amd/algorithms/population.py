@@ -30,6 +30,13 @@ call (or process), so the chaining contract holds for every rule.
 step updates the one a coin names with the other's value at its own arg-max -- the cure for the maximisation bias of
 ``max_a' Q[s', a']``.  The coin is the unused fourth word of the step's policy draws, so there is no new run state
 besides B.  DESIGN section 4.3c defines the step; ``tests/double_q_model.py`` restates it on the oracle.
+
+``n_step=n`` (2 .. 16; kernel ``k_nstep_rollout``) gives the on-policy rules the bootstrapping horizon of n-step TD
+(Sutton & Barto ch. 7): n-step SARSA and n-step Expected SARSA, the lever between TD(0) and Monte Carlo when reward
+arrives only at the end of an episode.  A run keeps a window of its last transitions; ``state_dict["n_step_window"]``
+carries it from call to call as ``pending_actions`` carries SARSA's action.  An uncorrected n-step Q-learning is not an
+off-policy method, so ``update_rule="q_learning"`` and ``double_q=True`` are refused with ``n_step > 1``.  DESIGN section
+4.3c defines the step; ``tests/n_step_model.py`` restates it on the oracle.
 """
 
 from __future__ import annotations
@@ -137,6 +144,27 @@ def pending_array(values, runs) -> np.ndarray | None:
     return np.ascontiguousarray(arr, dtype=np.int32)
 
 
+def window_arrays(window, runs, n_step) -> tuple | None:
+    """``n_step_window`` of a state dict as the ``(length, states, actions, rewards)`` arrays the library takes (None:
+    every window empty): int32 ``[runs]``, int32 ``[runs, n_step - 1]`` twice and float32 ``[runs, n_step - 1]``;
+    ``ValueError`` on anything else."""
+    if window is None:
+        return None
+    if not isinstance(window, dict) or sorted(window) != ["actions", "length", "rewards", "states"]:
+        msg = "n_step_window: expected a dict with the keys 'length', 'states', 'actions' and 'rewards'"
+        raise ValueError(msg)
+    out = []
+    for key, shape, kinds, dtype in (("length", (runs,), "iu", np.int32), ("states", (runs, n_step - 1), "iu", np.int32),
+                                     ("actions", (runs, n_step - 1), "iu", np.int32),
+                                     ("rewards", (runs, n_step - 1), "fiu", np.float32)):
+        arr = np.asarray(window[key])
+        if arr.shape != shape or arr.dtype.kind not in kinds:
+            msg = f"n_step_window[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got shape {arr.shape} of {arr.dtype}"
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(arr, dtype=dtype))
+    return tuple(out)
+
+
 def _per_run(value, runs, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != runs:
@@ -150,13 +178,13 @@ class QLearningPopulation:
     """``runs`` independent single-agent Q-learners over ``state_size`` x ``action_size`` (at most 64 actions).
 
     ``discount_factor``, ``lr_schedule`` and ``exploration_rate_schedule`` take one value / schedule for every run or a
-    sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa") and ``double_q`` (two tables per
-    run, Q-learning only) hold for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa"), ``double_q`` (two tables per
+    run, Q-learning only) and ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) hold for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
-                 update_rule="q_learning", double_q=False):
+                 update_rule="q_learning", double_q=False, n_step=1):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -176,8 +204,19 @@ class QLearningPopulation:
         if double_q and update_rule != "q_learning":
             msg = f"double_q=True is Double Q-learning: it needs update_rule='q_learning', got {update_rule!r}"
             raise ValueError(msg)
+        if isinstance(n_step, (bool, np.bool_)) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= _lib.N_STEP_MAX:
+            msg = f"n_step must be an integer in 1 .. {_lib.N_STEP_MAX}, got {n_step!r}"
+            raise ValueError(msg)
+        if n_step > 1 and double_q:
+            msg = f"n_step={n_step} with double_q=True: the double estimator is a one-step method"
+            raise ValueError(msg)
+        if n_step > 1 and update_rule == "q_learning":
+            msg = (f"n_step={n_step} needs update_rule='sarsa' or 'expected_sarsa': an uncorrected n-step Q-learning is not an "
+                   "off-policy method (importance sampling and tree backup are not built)")
+            raise ValueError(msg)
         self.update_rule = update_rule
         self.double_q = bool(double_q)
+        self.n_step = int(n_step)
         self.learn_mode = learn_mode
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.discount_factor = np.ascontiguousarray(_per_run(discount_factor, self.runs, "discount_factor"), dtype=np.float64)
@@ -197,6 +236,8 @@ class QLearningPopulation:
             _lib.check(self._lib.qe_population_set_update_rule(self._h, _lib.UPDATE_RULES[update_rule]))
         if self.double_q:
             _lib.check(self._lib.qe_population_set_double(self._h, 1))
+        if self.n_step > 1:
+            _lib.check(self._lib.qe_population_set_n_step(self._h, self.n_step))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -253,6 +294,36 @@ class QLearningPopulation:
     @pending_actions.setter
     def pending_actions(self, values) -> None:
         _lib.check(self._lib.qe_population_set_pending_actions(self._h, _lib.ptr(pending_array(values, self.runs), C.c_int32)))
+
+    @property
+    def n_step_window(self) -> dict | None:
+        """``n_step > 1``: every run's window of transitions not yet updated, a dict of ``length`` (int32 ``[runs]``),
+        ``states``, ``actions`` (int32 ``[runs, n_step - 1]``) and ``rewards`` (float32 ``[runs, n_step - 1]``); rows are
+        oldest first and unused slots hold 0.  ``n_step == 1``: None.  Setting None empties every window."""
+        if self.n_step == 1:
+            return None
+        shape = (self.runs, self.n_step - 1)
+        length = np.empty(self.runs, dtype=np.int32)
+        states, actions = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
+        rewards = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.qe_population_window(self._h, _lib.ptr(length, C.c_int32), _lib.ptr(states, C.c_int32),
+                                                  _lib.ptr(actions, C.c_int32), _lib.ptr(rewards, C.c_float)))
+        return {"length": length, "states": states, "actions": actions, "rewards": rewards}
+
+    @n_step_window.setter
+    def n_step_window(self, window) -> None:
+        if self.n_step == 1:
+            if window is not None:
+                msg = "a population with n_step=1 has no window"
+                raise ValueError(msg)
+            return
+        arrays = window_arrays(window, self.runs, self.n_step)
+        if arrays is None:
+            _lib.check(self._lib.qe_population_set_window(self._h, None, None, None, None))
+            return
+        length, states, actions, rewards = arrays
+        _lib.check(self._lib.qe_population_set_window(self._h, _lib.ptr(length, C.c_int32), _lib.ptr(states, C.c_int32),
+                                                      _lib.ptr(actions, C.c_int32), _lib.ptr(rewards, C.c_float)))
 
     def _rng_step(self):
         """``state_dict["rng_step"]``: an int while all runs agree, else the int64 array of every run's."""
@@ -367,7 +438,9 @@ class QLearningPopulation:
     def run_steps(self, steps, env, curr_state_dict=None, log=True) -> PopulationRun:
         """``steps`` steps of every run on ``env`` (a device environment of ``num_agents == runs``).  ``curr_state_dict``
         None resets the environment, as the reference's ``run_steps``; the dict of the previous call continues it
-        (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step).
+        (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step;
+        ``n_step > 1``: with its ``n_step_window``; after a reset, or without that key, every window starts empty and
+        the entries dropped are never updated).
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
         result, in which the other runs are unaffected)."""
@@ -380,6 +453,8 @@ class QLearningPopulation:
             env.restore(curr_state_dict["states"], curr_state_dict["rewards"], curr_state_dict.get("aux"))
         if self.update_rule == "sarsa":
             self.pending_actions = None if curr_state_dict is None else curr_state_dict.get("pending_actions")
+        if self.n_step > 1:
+            self.n_step_window = None if curr_state_dict is None else curr_state_dict.get("n_step_window")
         eps_d = self._descriptors(self.exploration_rate_schedules)
         lr_d = self._descriptors(self.lr_schedules)
         sched_p = C.POINTER(_lib.RunSchedule)
@@ -420,6 +495,8 @@ class QLearningPopulation:
         state_dict["exploration_rate"] = eps_v
         if self.update_rule == "sarsa":
             state_dict["pending_actions"] = self.pending_actions
+        if self.n_step > 1:
+            state_dict["n_step_window"] = self.n_step_window
         result = PopulationRun(means, counts, rets, offsets, at, state_dict)
         if empty:
             bad = np.flatnonzero(status).tolist()
@@ -431,10 +508,12 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter(s), every run's schedule values and (SARSA) pending action.  Tables: :meth:`load`; environments: pass
+        counter(s), every run's schedule values, (SARSA) pending action and (``n_step > 1``) window.  Tables: :meth:`load`; environments: pass
         the dict to ``run_steps``."""
         if self.update_rule == "sarsa":
             self.pending_actions = state_dict.get("pending_actions")
+        if self.n_step > 1:
+            self.n_step_window = state_dict.get("n_step_window")
         rng_step = state_dict["rng_step"]
         if np.ndim(rng_step) == 0:
             self.step_counter = int(rng_step)
@@ -565,4 +644,4 @@ class QLearningPopulation:
 
 
 __all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "pending_array", "schedule_descriptor"]
+           "pending_array", "schedule_descriptor", "window_arrays"]

@@ -397,4 +397,21 @@ struct Td<double> {
     }
 };
 
+// The target y of Td<T>::apply for (r, m, term) in learn mode `mode`, rounded once to the table dtype: the operations
+// and their order are those of apply / vec_inc / delta above.  The n-step rules (qe_rollout_nstep.h) fold a window of
+// rewards with it, g_i = td_target(r_i, g_{i+1}, term_i), and hand the result to apply as its bootstrap scalar.
+__device__ __forceinline__ float td_target(float r, float m, bool term, const Hyper& h, int mode) {
+    if (mode == 0) {
+        const float t = term ? 0.0f : h.gamma32 * m;
+        return r + t;
+    }
+    const float t32 = h.gamma32 * m;
+    const double t = (double)t32 * (term ? 0.0 : 1.0);
+    return (float)((double)r + t);
+}
+__device__ __forceinline__ double td_target(float r, double m, bool term, const Hyper& h, int mode) {
+    const double t = mode == 1 ? (h.gamma * m) * (term ? 0.0 : 1.0) : (term ? 0.0 : h.gamma * m);
+    return (double)r + t;
+}
+
 }  // namespace qe

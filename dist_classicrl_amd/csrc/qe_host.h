@@ -25,6 +25,10 @@
 
 using namespace qe;
 
+namespace qe {
+struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
+}
+
 // records the text qe_last_error() returns (thread-local) and hands `code` back
 __attribute__((visibility("hidden"))) int qe_fail(int code, const char* fmt, ...);
 
@@ -180,12 +184,20 @@ struct PopState {
     // Double estimator (qe_population_set_double): table B, the engine's dtype, shape and row stride; the engine's own
     // table is A.  NULL: off (k_double_rollout / k_double_evaluate, qe_rollout_double.h).
     void* table_b = nullptr;
+    // n-step rules (qe_population_set_n_step): the horizon, 1 = the one-step kernels above.  n_step > 1: every run's
+    // window of at most n_step - 1 transitions between launches, [slot][runs], oldest first (k_nstep_rollout,
+    // qe_rollout_nstep.h); allocated when n_step is set.
+    int n_step = 1;
+    DevBuf<int32_t> win_len, win_s, win_a;
+    DevBuf<float> win_r;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
         seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
         h_cnt.release(); h_step.release(); h_ret.release();
         step_off.release(); used.release(); done.release(); h_done.release(); pending.release();
+        win_len.release(); win_s.release(); win_a.release(); win_r.release();
+        n_step = 1;
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
         off_any = false;
@@ -409,7 +421,9 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   masked environment; path 6 = population (k_rollout_runs) and path 7 = population greedy evaluation
 //   (k_evaluate_runs), both with the same NV and masked bits; path 8 = population with an on-policy update rule
 //   (k_rollout_runs_td): those NV and masked bits, and the rule (qe_update_rule) in bits 4-5; path 9 = population with
-//   the double estimator (k_double_rollout) and path 10 = its greedy evaluation (k_double_evaluate), NV and masked bits
+//   the double estimator (k_double_rollout) and path 10 = its greedy evaluation (k_double_evaluate), NV and masked bits;
+//   path 11 = population with an n-step on-policy rule (k_nstep_rollout): the rule in bits 4-5, NV and masked as path 6,
+//   and n in bits 24-28, which no other path uses
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -419,6 +433,7 @@ constexpr int64_t QE_VARIANT_RUNS_EVAL = 7;  // population greedy evaluation (k_
 constexpr int64_t QE_VARIANT_RUNS_TD = 8;  // population, SARSA / Expected SARSA (k_rollout_runs_td): + the rule in bits 4-5
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE = 9;        // population, Double Q-learning (k_double_rollout): NV and masked bits
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE_EVAL = 10;  // ... and its greedy evaluation (k_double_evaluate)
+constexpr int64_t QE_VARIANT_RUNS_NSTEP = 11;  // population, n-step SARSA / Expected SARSA (k_nstep_rollout): as path 8, + n in bits 24-28
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -427,7 +442,7 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
-// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip): go(integral_constant<int, NV>, bool_constant<masked>).
 template <class Env, class F>
 inline int64_t runs_by_build(int ld, bool masked, F go) {
     using Yes = std::true_type;
@@ -456,6 +471,10 @@ int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, i
 template <typename T, class Env>
 int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
                        int32_t* pending);
+// ... with the n-step form of that rule and the runs' windows `w` (qe_inst_runs_nstep.hip)
+template <typename T, class Env>
+int64_t launch_nstep_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
+                          int32_t* pending, const NStepWin& w);
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,

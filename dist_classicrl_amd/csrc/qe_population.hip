@@ -4,8 +4,11 @@
 // (qe_rollout_runs.h, instantiated in qe_inst_runs.hip), plus the compaction of the per-run episode-log segments and
 // the per-run draw counters.  With the double estimator on (qe_population_set_double) a second table B of the same
 // shape stands beside the engine's table A: k_double_rollout trains both and k_double_evaluate acts on their sum
-// (qe_rollout_double.h, instantiated in qe_inst_runs_double.hip).
+// (qe_rollout_double.h, instantiated in qe_inst_runs_double.hip).  With a horizon n > 1 (qe_population_set_n_step) the
+// on-policy rules train through k_nstep_rollout (qe_rollout_nstep.h, instantiated in qe_inst_runs_nstep.hip), which
+// carries every run's window of transitions from launch to launch in the win_* arrays.
 #include "qe_host.h"
+#include "qe_rollout_nstep.h"
 
 namespace {
 
@@ -192,6 +195,16 @@ int pending_reserve(qe_engine* e) {
     return QE_OK;
 }
 
+// The n-step rules' windows, [slot][runs] with n - 1 slots: allocated for the horizon `n`, every window empty.
+int window_reserve(qe_engine* e, int n) {
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs, cells = m * (size_t)(n - 1);
+    HIP_TRY(P.win_len.ensure(m)); HIP_TRY(P.win_s.ensure(cells)); HIP_TRY(P.win_a.ensure(cells)); HIP_TRY(P.win_r.ensure(cells));
+    HIP_TRY(hipMemsetAsync(P.win_len.p, 0, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 // The double estimator's table entry points: the qe_table_* call `f` with table B standing in for the engine's table.
 template <class F>
 int on_table_b(qe_engine* e, F f) {
@@ -326,6 +339,10 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
                 if (P.table_b) return launch_double_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, (T*)P.table_b);
+                if (P.n_step > 1) {
+                    const NStepWin w{P.n_step, P.win_len.p, P.win_s.p, P.win_a.p, P.win_r.p};
+                    return launch_nstep_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
+                }
                 if (P.rule != QE_RULE_Q_LEARNING)
                     return launch_runs_td<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p);
                 return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
@@ -501,6 +518,11 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
         return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
     if (e->pop.table_b && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (qe_population_set_double)");
+    if (e->pop.n_step > 1 && rule == QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (importance sampling and "
+                       "tree backup are not built); the n-step rules are SARSA and Expected SARSA",
+                       e->pop.n_step);
     e->pop.rule = rule;
     return QE_OK;
 }
@@ -513,6 +535,8 @@ int qe_population_update_rule(qe_engine* e) {
 int qe_population_set_double(qe_engine* e, int32_t on) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
+    if (on && P.n_step > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.n_step);
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", P.rule);
     HIP_TRY(hipSetDevice(e->device));
@@ -592,6 +616,97 @@ int qe_population_set_pending_actions(qe_engine* e, const int32_t* in) {
     if (int rc = pending_reserve(e)) return rc;
     if (in) HIP_TRY(hipMemcpyAsync(e->pop.pending.p, in, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     else HIP_TRY(hipMemsetAsync(e->pop.pending.p, 0xFF, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_set_n_step(qe_engine* e, int32_t n) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (n < 1 || n > NSTEP_MAX) return qe_fail(QE_ERR_INVALID, "n_step must be in 1 .. %d, got %d", NSTEP_MAX, (int)n);
+    if (n > 1 && P.rule == QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "n_step = %d with Q-learning: an uncorrected n-step Q-learning is not an off-policy method (importance "
+                       "sampling and tree backup are not built); the n-step rules are SARSA and Expected SARSA",
+                       (int)n);
+    if (n > 1 && P.table_b)
+        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
+    if (n == P.n_step) return QE_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (n > 1) {
+        if (int rc = window_reserve(e, n)) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        P.win_len.release(); P.win_s.release(); P.win_a.release(); P.win_r.release();
+    }
+    P.n_step = n;
+    return QE_OK;
+}
+
+int qe_population_n_step(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    return e->pop.n_step;
+}
+
+int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs, w = (size_t)(P.n_step - 1);
+    if (!w) return QE_OK;  // a one-step rule has no window: nothing to write
+    if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hs(m * w), ha(m * w);
+    std::vector<float> hr(m * w);
+    HIP_TRY(hipMemcpyAsync(len, P.win_len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), P.win_s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), P.win_a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), P.win_r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t r = 0; r < m; ++r)  // [slot][run] -> [run][slot]; slots past the length hold 0
+        for (size_t i = 0; i < w; ++i) {
+            const bool used = (int32_t)i < len[r];
+            if (states) states[r * w + i] = used ? hs[i * m + r] : 0;
+            if (actions) actions[r * w + i] = used ? ha[i * m + r] : 0;
+            if (rewards) rewards[r * w + i] = used ? hr[i * m + r] : 0.0f;
+        }
+    return QE_OK;
+}
+
+int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
+                             const float* rewards) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs, w = (size_t)(P.n_step - 1);
+    if (!w) {
+        for (size_t r = 0; len && r < m; ++r)
+            if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with n_step = 1", (long long)r, (int)len[r]);
+        return QE_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!len) {  // every window empty
+        HIP_TRY(hipMemsetAsync(P.win_len.p, 0, m * sizeof(int32_t), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return QE_OK;
+    }
+    if (!states || !actions || !rewards) return qe_fail(QE_ERR_INVALID, "states, actions or rewards is NULL");
+    std::vector<int32_t> hs(m * w, 0), ha(m * w, 0);
+    std::vector<float> hr(m * w, 0.0f);
+    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
+        if (len[r] < 0 || len[r] > (int32_t)w)
+            return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
+        for (size_t i = 0; i < (size_t)len[r]; ++i) {
+            const int32_t s = states[r * w + i], a = actions[r * w + i];
+            if (s < 0 || s >= P.S)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)P.S);
+            if (a < 0 || a >= e->A)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
+            hs[i * m + r] = s; ha[i * m + r] = a; hr[i * m + r] = rewards[r * w + i];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(P.win_len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win_s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win_a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win_r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }

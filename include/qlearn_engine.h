@@ -95,7 +95,9 @@ typedef struct qe_rollout_stats {
                                 an on-policy update rule (SARSA / Expected SARSA): those NV and masked bits, and the rule
                                 (qe_update_rule) in bits 4-5; path 9: population with the double estimator (Double
                                 Q-learning, qe_population_set_double) and path 10: its greedy evaluation, both with
-                                the NV and masked bits of path 6 */
+                                the NV and masked bits of path 6; path 11: population with an n-step on-policy rule
+                                (qe_population_set_n_step): the rule in bits 4-5, NV and masked as path 6, and n in
+                                bits 24-28, which no other path uses */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -349,7 +351,24 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         qe_population_set_update_rule to another rule while the switch is on.  qe_population_double
  *                         returns 1 / 0 (or a negative qe_status).
  *   qe_population_table_b_upload / _download / _download_rows  qe_table_upload / qe_table_download /
- *                         qe_table_download_rows on table B; QE_ERR_INVALID while the switch is off. */
+ *                         qe_table_download_rows on table B; QE_ERR_INVALID while the switch is off.
+ *   qe_population_set_n_step / qe_population_n_step  the bootstrapping horizon n of the on-policy rules, 1 (the default:
+ *                         the one-step rules above) .. 16: n-step SARSA and n-step Expected SARSA (Sutton & Barto ch. 7).
+ *                         A run keeps a window of its last transitions (s, a, r), at most n - 1 between steps.  Each step
+ *                         appends one; a window of n entries updates and drops its oldest one, a terminated step updates
+ *                         all of them, oldest first, and empties the window.  Entry j bootstraps from the fold of the
+ *                         later rewards onto the one-step rule's scalar v of this step: g_L = v, g_i = T(r_i + gamma *
+ *                         g_{i+1}), with the arithmetic of the learn mode.  Setting n empties every window.  Not a
+ *                         population engine or n out of range -> QE_ERR_INVALID.  n > 1 while the rule is Q-learning (an
+ *                         uncorrected n-step Q-learning is no off-policy method) or the double switch is on ->
+ *                         QE_ERR_UNSUPPORTED, and so is switching to either of those while n > 1.  Greedy evaluation
+ *                         neither reads nor clears the windows.
+ *   qe_population_window / qe_population_set_window  the windows, run state besides the tables and the pending actions:
+ *                         `len` has `runs` entries (0 .. n - 1), `states`, `actions` and `rewards` runs * (n - 1), run r's
+ *                         entries at [r * (n - 1) + i], oldest first; unused slots read 0 and are ignored when set.  The
+ *                         rollout leaves them behind; set them (len NULL: every window empty, its entries are never
+ *                         updated) when the environment state is restored or reset.  A length above n - 1, or a state or
+ *                         action outside the table -> QE_ERR_INVALID.  With n = 1 there is nothing to read or set. */
 enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
 typedef struct qe_run_schedule {
@@ -381,6 +400,11 @@ int qe_population_double(qe_engine* e);
 int qe_population_table_b_upload(qe_engine* e, const void* host, int32_t host_dtype);
 int qe_population_table_b_download(qe_engine* e, void* host, int32_t host_dtype);
 int qe_population_table_b_download_rows(qe_engine* e, void* host, int64_t first_row, int64_t rows);
+int qe_population_set_n_step(qe_engine* e, int32_t n);
+int qe_population_n_step(qe_engine* e);
+int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards);
+int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
+                             const float* rewards);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its
