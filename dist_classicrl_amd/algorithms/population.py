@@ -37,6 +37,16 @@ arrives only at the end of an episode.  A run keeps a window of its last transit
 carries it from call to call as ``pending_actions`` carries SARSA's action.  An uncorrected n-step Q-learning is not an
 off-policy method, so ``update_rule="q_learning"`` and ``double_q=True`` are refused with ``n_step > 1``.  DESIGN section
 4.3c defines the step; ``tests/n_step_model.py`` restates it on the oracle.
+
+``trace_decay=lam`` (one lambda in [0, 1] or one per run; kernel ``k_trace_rollout``) turns on eligibility traces
+(Sutton & Barto ch. 12): SARSA(lambda) under ``update_rule="sarsa"``, Watkins's Q(lambda) under ``"q_learning"`` -- the
+multi-step method that updates backwards at every step instead of ``n`` steps late, and the one Q-learning has.  A run
+keeps ``trace_length`` slots ``(s, a, e)``, a truncated sparse trace table: a step marks its cell (``trace_kind``
+"replacing": e = 1, "accumulating": e + 1; a full table drops its smallest trace), adds ``u * e`` to every live cell, u
+the one-step rule's increment, and decays every trace by ``gamma * lam``; Q(lambda) cuts all traces at a non-greedy
+action.  ``state_dict["eligibility_traces"]`` carries the slots from call to call.  ``update_rule="expected_sarsa"``,
+``double_q=True`` and ``n_step > 1`` are refused with traces.  DESIGN section 4.3c defines the step;
+``tests/trace_model.py`` restates it on the oracle.
 """
 
 from __future__ import annotations
@@ -165,6 +175,26 @@ def window_arrays(window, runs, n_step) -> tuple | None:
     return tuple(out)
 
 
+def trace_arrays(traces, runs, trace_length) -> tuple | None:
+    """``eligibility_traces`` of a state dict as the ``(states, actions, values)`` arrays the library takes (None: every
+    slot free): int32 ``[runs, trace_length]`` twice and float64 ``[runs, trace_length]``; ``ValueError`` on anything
+    else."""
+    if traces is None:
+        return None
+    if not isinstance(traces, dict) or sorted(traces) != ["actions", "states", "values"]:
+        msg = "eligibility_traces: expected a dict with the keys 'states', 'actions' and 'values'"
+        raise ValueError(msg)
+    out = []
+    shape = (runs, trace_length)
+    for key, kinds, dtype in (("states", "iu", np.int32), ("actions", "iu", np.int32), ("values", "fiu", np.float64)):
+        arr = np.asarray(traces[key])
+        if arr.shape != shape or arr.dtype.kind not in kinds:
+            msg = f"eligibility_traces[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got shape {arr.shape} of {arr.dtype}"
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(arr, dtype=dtype))
+    return tuple(out)
+
+
 def _per_run(value, runs, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != runs:
@@ -179,12 +209,16 @@ class QLearningPopulation:
 
     ``discount_factor``, ``lr_schedule`` and ``exploration_rate_schedule`` take one value / schedule for every run or a
     sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa"), ``double_q`` (two tables per
-    run, Q-learning only) and ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) hold for all of them.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    run, Q-learning only) and ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) hold for all of them.
+    ``trace_decay`` (None: no traces; else one lambda in [0, 1] or a sequence of ``runs``) turns on eligibility traces for
+    "sarsa" and "q_learning", with ``trace_length`` slots per run (1 .. 32) of ``trace_kind`` "replacing" or
+    "accumulating".  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
-                 update_rule="q_learning", double_q=False, n_step=1):
+                 update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
+                 trace_kind="replacing"):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -220,6 +254,47 @@ class QLearningPopulation:
         self.learn_mode = learn_mode
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.discount_factor = np.ascontiguousarray(_per_run(discount_factor, self.runs, "discount_factor"), dtype=np.float64)
+        self.trace_decay = None
+        self.trace_length = 0
+        self.trace_kind = None
+        if trace_decay is not None:
+            if update_rule == "expected_sarsa":
+                msg = ("trace_decay with update_rule='expected_sarsa': its trace form needs policy-probability weighting, which "
+                       "is not built; the trace rules are 'sarsa' and 'q_learning'")
+                raise ValueError(msg)
+            if double_q:
+                msg = "trace_decay with double_q=True: the double estimator has no trace form"
+                raise ValueError(msg)
+            if n_step > 1:
+                msg = f"trace_decay with n_step={n_step}: one multi-step method at a time"
+                raise ValueError(msg)
+            if (isinstance(trace_length, (bool, np.bool_)) or not isinstance(trace_length, (int, np.integer))
+                    or not 1 <= trace_length <= _lib.TRACE_MAX):
+                msg = f"trace_length must be an integer in 1 .. {_lib.TRACE_MAX}, got {trace_length!r}"
+                raise ValueError(msg)
+            if trace_kind not in _lib.TRACE_KINDS:
+                msg = f"trace_kind must be one of {', '.join(map(repr, _lib.TRACE_KINDS))}, got {trace_kind!r}"
+                raise ValueError(msg)
+            try:
+                lam = np.ascontiguousarray(_per_run(trace_decay, self.runs, "trace_decay"), dtype=np.float64)
+            except (TypeError, ValueError) as err:
+                if "one entry per run" in str(err):
+                    raise
+                msg = f"trace_decay must be None, a number in [0, 1] or a sequence of {self.runs}, got {trace_decay!r}"
+                raise ValueError(msg) from err
+            if lam.shape != (self.runs,) or not ((lam >= 0) & (lam <= 1)).all():
+                msg = f"trace_decay: every lambda must be a finite number in [0, 1], got {trace_decay!r}"
+                raise ValueError(msg)
+            with np.errstate(all="ignore"):
+                decay = (self.discount_factor * lam).astype(self.dtype)  # what the kernel multiplies the traces by
+            if not ((decay >= 0) & (decay <= 1)).all():
+                r = int(np.flatnonzero(~((decay >= 0) & (decay <= 1)))[0])
+                msg = (f"trace_decay: run {r}'s decay factor discount_factor * trace_decay = {self.discount_factor[r]!r} * "
+                       f"{lam[r]!r} is outside [0, 1]")
+                raise ValueError(msg)
+            self.trace_decay = lam
+            self.trace_length = int(trace_length)
+            self.trace_kind = trace_kind
         lr_schedule = ConstantSchedule(0.1) if lr_schedule is None else lr_schedule
         exploration_rate_schedule = ConstantSchedule(0.1) if exploration_rate_schedule is None else exploration_rate_schedule
         self.lr_schedules = _per_run(lr_schedule, self.runs, "lr_schedule")
@@ -238,6 +313,9 @@ class QLearningPopulation:
             _lib.check(self._lib.qe_population_set_double(self._h, 1))
         if self.n_step > 1:
             _lib.check(self._lib.qe_population_set_n_step(self._h, self.n_step))
+        if self.trace_decay is not None:
+            _lib.check(self._lib.qe_population_set_traces(self._h, self.trace_length, _lib.TRACE_KINDS[self.trace_kind],
+                                                          _lib.ptr(self.trace_decay, C.c_double)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -324,6 +402,35 @@ class QLearningPopulation:
         length, states, actions, rewards = arrays
         _lib.check(self._lib.qe_population_set_window(self._h, _lib.ptr(length, C.c_int32), _lib.ptr(states, C.c_int32),
                                                       _lib.ptr(actions, C.c_int32), _lib.ptr(rewards, C.c_float)))
+
+    @property
+    def eligibility_traces(self) -> dict | None:
+        """``trace_decay`` set: every run's trace slots, a dict of ``states``, ``actions`` (int32 ``[runs, trace_length]``)
+        and ``values`` (float64 ``[runs, trace_length]``, exact for either dtype), in slot order; free slots read
+        ``(0, 0, 0.0)``.  Without traces: None.  Setting None frees every slot."""
+        if self.trace_decay is None:
+            return None
+        shape = (self.runs, self.trace_length)
+        states, actions = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
+        values = np.empty(shape, dtype=np.float64)
+        _lib.check(self._lib.qe_population_traces(self._h, _lib.ptr(states, C.c_int32), _lib.ptr(actions, C.c_int32),
+                                                  _lib.ptr(values, C.c_double)))
+        return {"states": states, "actions": actions, "values": values}
+
+    @eligibility_traces.setter
+    def eligibility_traces(self, traces) -> None:
+        if self.trace_decay is None:
+            if traces is not None:
+                msg = "a population without trace_decay has no eligibility traces"
+                raise ValueError(msg)
+            return
+        arrays = trace_arrays(traces, self.runs, self.trace_length)
+        if arrays is None:
+            _lib.check(self._lib.qe_population_set_trace_state(self._h, None, None, None))
+            return
+        states, actions, values = arrays
+        _lib.check(self._lib.qe_population_set_trace_state(self._h, _lib.ptr(states, C.c_int32), _lib.ptr(actions, C.c_int32),
+                                                           _lib.ptr(values, C.c_double)))
 
     def _rng_step(self):
         """``state_dict["rng_step"]``: an int while all runs agree, else the int64 array of every run's."""
@@ -440,7 +547,8 @@ class QLearningPopulation:
         None resets the environment, as the reference's ``run_steps``; the dict of the previous call continues it
         (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step;
         ``n_step > 1``: with its ``n_step_window``; after a reset, or without that key, every window starts empty and
-        the entries dropped are never updated).
+        the entries dropped are never updated; ``trace_decay``: with its ``eligibility_traces``; after a reset, or
+        without that key, every slot starts free).
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
         result, in which the other runs are unaffected)."""
@@ -455,6 +563,8 @@ class QLearningPopulation:
             self.pending_actions = None if curr_state_dict is None else curr_state_dict.get("pending_actions")
         if self.n_step > 1:
             self.n_step_window = None if curr_state_dict is None else curr_state_dict.get("n_step_window")
+        if self.trace_decay is not None:
+            self.eligibility_traces = None if curr_state_dict is None else curr_state_dict.get("eligibility_traces")
         eps_d = self._descriptors(self.exploration_rate_schedules)
         lr_d = self._descriptors(self.lr_schedules)
         sched_p = C.POINTER(_lib.RunSchedule)
@@ -497,6 +607,8 @@ class QLearningPopulation:
             state_dict["pending_actions"] = self.pending_actions
         if self.n_step > 1:
             state_dict["n_step_window"] = self.n_step_window
+        if self.trace_decay is not None:
+            state_dict["eligibility_traces"] = self.eligibility_traces
         result = PopulationRun(means, counts, rets, offsets, at, state_dict)
         if empty:
             bad = np.flatnonzero(status).tolist()
@@ -508,12 +620,14 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter(s), every run's schedule values, (SARSA) pending action and (``n_step > 1``) window.  Tables: :meth:`load`; environments: pass
+        counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``) window and (``trace_decay``) trace slots.  Tables: :meth:`load`; environments: pass
         the dict to ``run_steps``."""
         if self.update_rule == "sarsa":
             self.pending_actions = state_dict.get("pending_actions")
         if self.n_step > 1:
             self.n_step_window = state_dict.get("n_step_window")
+        if self.trace_decay is not None:
+            self.eligibility_traces = state_dict.get("eligibility_traces")
         rng_step = state_dict["rng_step"]
         if np.ndim(rng_step) == 0:
             self.step_counter = int(rng_step)
@@ -644,4 +758,4 @@ class QLearningPopulation:
 
 
 __all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "pending_array", "schedule_descriptor", "window_arrays"]
+           "pending_array", "schedule_descriptor", "trace_arrays", "window_arrays"]

@@ -27,6 +27,8 @@ using namespace qe;
 
 namespace qe {
 struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
+template <typename T>
+struct TraceSlots;  // the slots of the eligibility traces (qe_rollout_trace.h)
 }
 
 // records the text qe_last_error() returns (thread-local) and hands `code` back
@@ -190,6 +192,14 @@ struct PopState {
     int n_step = 1;
     DevBuf<int32_t> win_len, win_s, win_a;
     DevBuf<float> win_r;
+    // Eligibility traces (qe_population_set_traces): trace_k slots per run, 0 = off (the kernels above).  On: every
+    // run's slots between launches, [slot][runs] (trace_e holds trace_k * runs values of the table dtype; a slot whose
+    // value is 0 is free), and every run's lambda (k_trace_rollout, qe_rollout_trace.h); allocated when traces are set.
+    int trace_k = 0, trace_kind = 0;
+    DevBuf<int32_t> trace_s, trace_a;
+    DevBuf<double> trace_e;
+    DevBuf<double> trace_lambda;
+    std::vector<double> h_lambda;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
@@ -198,6 +208,9 @@ struct PopState {
         step_off.release(); used.release(); done.release(); h_done.release(); pending.release();
         win_len.release(); win_s.release(); win_a.release(); win_r.release();
         n_step = 1;
+        trace_s.release(); trace_a.release(); trace_e.release(); trace_lambda.release();
+        h_lambda.clear();
+        trace_k = 0;
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
         off_any = false;
@@ -423,7 +436,9 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   (k_rollout_runs_td): those NV and masked bits, and the rule (qe_update_rule) in bits 4-5; path 9 = population with
 //   the double estimator (k_double_rollout) and path 10 = its greedy evaluation (k_double_evaluate), NV and masked bits;
 //   path 11 = population with an n-step on-policy rule (k_nstep_rollout): the rule in bits 4-5, NV and masked as path 6,
-//   and n in bits 24-28, which no other path uses
+//   and n in bits 24-28, which no other path uses; path 12 = population with eligibility traces (k_trace_rollout): the
+//   rule in bits 4-5 (0 = Watkins's Q(lambda), 1 = SARSA(lambda)), NV and masked as path 6, K in bits 24-29 and the trace
+//   kind in bit 30, which no other field of that path uses
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -434,6 +449,7 @@ constexpr int64_t QE_VARIANT_RUNS_TD = 8;  // population, SARSA / Expected SARSA
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE = 9;        // population, Double Q-learning (k_double_rollout): NV and masked bits
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE_EVAL = 10;  // ... and its greedy evaluation (k_double_evaluate)
 constexpr int64_t QE_VARIANT_RUNS_NSTEP = 11;  // population, n-step SARSA / Expected SARSA (k_nstep_rollout): as path 8, + n in bits 24-28
+constexpr int64_t QE_VARIANT_RUNS_TRACE = 12;  // population, SARSA(lambda) / Watkins's Q(lambda) (k_trace_rollout): + K in bits 24-29, kind in bit 30
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -442,7 +458,7 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
-// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip, qe_inst_runs_trace.hip): go(integral_constant<int, NV>, bool_constant<masked>).
 template <class Env, class F>
 inline int64_t runs_by_build(int ld, bool masked, F go) {
     using Yes = std::true_type;
@@ -475,6 +491,10 @@ int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev
 template <typename T, class Env>
 int64_t launch_nstep_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
                           int32_t* pending, const NStepWin& w);
+// ... with eligibility traces: `rule` is QE_RULE_Q_LEARNING or QE_RULE_SARSA, `w` the runs' slots (qe_inst_runs_trace.hip)
+template <typename T, class Env>
+int64_t launch_trace_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
+                          int32_t* pending, const TraceSlots<T>& w);
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,

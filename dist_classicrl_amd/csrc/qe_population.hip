@@ -6,9 +6,12 @@
 // shape stands beside the engine's table A: k_double_rollout trains both and k_double_evaluate acts on their sum
 // (qe_rollout_double.h, instantiated in qe_inst_runs_double.hip).  With a horizon n > 1 (qe_population_set_n_step) the
 // on-policy rules train through k_nstep_rollout (qe_rollout_nstep.h, instantiated in qe_inst_runs_nstep.hip), which
-// carries every run's window of transitions from launch to launch in the win_* arrays.
+// carries every run's window of transitions from launch to launch in the win_* arrays.  With eligibility traces on
+// (qe_population_set_traces) SARSA and Q-learning train through k_trace_rollout (qe_rollout_trace.h, instantiated in
+// qe_inst_runs_trace.hip), which carries every run's trace slots from launch to launch in the trace_* arrays.
 #include "qe_host.h"
 #include "qe_rollout_nstep.h"
+#include "qe_rollout_trace.h"
 
 namespace {
 
@@ -205,6 +208,34 @@ int window_reserve(qe_engine* e, int n) {
     return QE_OK;
 }
 
+// T(gamma * lambda), the decay factor of a run's traces, as a double; `f32`: T is float.
+double trace_decay_of(double gamma, double lambda, bool f32) {
+    const double d = gamma * lambda;
+    return f32 ? (double)(float)d : d;
+}
+
+// QE_ERR_UNSUPPORTED naming the first run whose decay factor lies outside [0, 1] (a NaN included), else QE_OK.
+int check_trace_decay(const qe_engine* e, const double* gamma, const double* lambda) {
+    for (size_t r = 0; r < (size_t)e->pop.runs; ++r) {
+        const double d = trace_decay_of(gamma[r], lambda[r], e->dtype == QE_F32);
+        if (!(d >= 0.0 && d <= 1.0))
+            return qe_fail(QE_ERR_UNSUPPORTED, "run %lld: the trace decay factor gamma * lambda = %g * %g is outside [0, 1]",
+                           (long long)r, gamma[r], lambda[r]);
+    }
+    return QE_OK;
+}
+
+// Every trace slot of every run free.
+int traces_clear(qe_engine* e) {
+    PopState& P = e->pop;
+    const size_t cells = (size_t)P.runs * (size_t)P.trace_k;
+    HIP_TRY(hipMemsetAsync(P.trace_s.p, 0, cells * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.trace_a.p, 0, cells * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.trace_e.p, 0, cells * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 // The double estimator's table entry points: the qe_table_* call `f` with table B standing in for the engine's table.
 template <class F>
 int on_table_b(qe_engine* e, F f) {
@@ -264,6 +295,8 @@ int qe_population_configure(qe_engine* e, const qe_run_schedule* eps, const qe_r
     if (int rc = need_population(e)) return rc;
     static_assert(sizeof(qe_run_schedule) == sizeof(RunSched), "qe_run_schedule and RunSched differ");
     const size_t m = (size_t)e->pop.runs;
+    if (gamma && e->pop.trace_k)  // (the kernel multiplies the traces by T(gamma * lambda))
+        if (int rc = check_trace_decay(e, gamma, e->pop.h_lambda.data())) return rc;
     for (const qe_run_schedule* d : {eps, lr})
         for (size_t r = 0; d && r < m; ++r)
             if (d[r].kind < QE_SCHED_CONSTANT || d[r].kind > QE_SCHED_EXPONENTIAL)
@@ -339,6 +372,10 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
                 if (P.table_b) return launch_double_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, (T*)P.table_b);
+                if (P.trace_k) {
+                    const TraceSlots<T> w{P.trace_k, P.trace_kind, P.trace_s.p, P.trace_a.p, (T*)P.trace_e.p, P.trace_lambda.p};
+                    return launch_trace_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
+                }
                 if (P.n_step > 1) {
                     const NStepWin w{P.n_step, P.win_len.p, P.win_s.p, P.win_a.p, P.win_r.p};
                     return launch_nstep_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
@@ -523,6 +560,10 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
                        "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (importance sampling and "
                        "tree backup are not built); the n-step rules are SARSA and Expected SARSA",
                        e->pop.n_step);
+    if (e->pop.trace_k && rule == QE_RULE_EXPECTED_SARSA)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "eligibility traces are on: the trace form of Expected SARSA needs policy-probability weighting, which "
+                       "is not built; the trace rules are SARSA and Q-learning (qe_population_set_traces)");
     e->pop.rule = rule;
     return QE_OK;
 }
@@ -537,6 +578,8 @@ int qe_population_set_double(qe_engine* e, int32_t on) {
     PopState& P = e->pop;
     if (on && P.n_step > 1)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.n_step);
+    if (on && P.trace_k)
+        return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces are on: the double estimator has no trace form (qe_population_set_traces)");
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", P.rule);
     HIP_TRY(hipSetDevice(e->device));
@@ -631,6 +674,8 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
                        (int)n);
     if (n > 1 && P.table_b)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
+    if (n > 1 && P.trace_k)
+        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
     if (n == P.n_step) return QE_OK;
     HIP_TRY(hipSetDevice(e->device));
     if (n > 1) {
@@ -707,6 +752,122 @@ int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* st
     HIP_TRY(hipMemcpyAsync(P.win_s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(P.win_a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(P.win_r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double* lambda) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    if (!lambda) {  // off
+        if (!P.trace_k) return QE_OK;
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        P.trace_s.release(); P.trace_a.release(); P.trace_e.release(); P.trace_lambda.release();
+        P.h_lambda.clear();
+        P.trace_k = 0;
+        return QE_OK;
+    }
+    if (K < 1 || K > TRACE_MAX) return qe_fail(QE_ERR_INVALID, "trace_length must be in 1 .. %d, got %d", TRACE_MAX, (int)K);
+    if (kind != QE_TRACE_REPLACING && kind != QE_TRACE_ACCUMULATING)
+        return qe_fail(QE_ERR_INVALID, "unknown trace kind %d (qe_trace_kind)", (int)kind);
+    for (size_t r = 0; r < m; ++r)
+        if (!(lambda[r] >= 0.0 && lambda[r] <= 1.0))
+            return qe_fail(QE_ERR_UNSUPPORTED, "trace decay of run %lld: lambda = %g is outside [0, 1]", (long long)r, lambda[r]);
+    if (P.rule == QE_RULE_EXPECTED_SARSA)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "eligibility traces with Expected SARSA: its trace form needs policy-probability weighting, which is not "
+                       "built; the trace rules are SARSA and Q-learning");
+    if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces: the double estimator has no trace form (qe_population_set_double)");
+    if (P.n_step > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces with n_step = %d: one multi-step method at a time (qe_population_set_n_step)", P.n_step);
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<double> gamma(m);
+    HIP_TRY(hipMemcpyAsync(gamma.data(), P.gamma.p, m * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (int rc = check_trace_decay(e, gamma.data(), lambda)) return rc;
+    const size_t cells = m * (size_t)K;
+    HIP_TRY(P.trace_s.ensure(cells)); HIP_TRY(P.trace_a.ensure(cells)); HIP_TRY(P.trace_e.ensure(cells)); HIP_TRY(P.trace_lambda.ensure(m));
+    HIP_TRY(hipMemcpyAsync(P.trace_lambda.p, lambda, m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    P.h_lambda.assign(lambda, lambda + m);
+    P.trace_k = K;
+    P.trace_kind = kind;
+    return traces_clear(e);
+}
+
+int qe_population_trace_config(qe_engine* e, int32_t* K, int32_t* kind, double* lambda) {
+    if (int rc = need_population(e)) return rc;
+    const PopState& P = e->pop;
+    if (K) *K = P.trace_k;
+    if (kind) *kind = P.trace_k ? P.trace_kind : 0;
+    if (lambda && P.trace_k) std::copy(P.h_lambda.begin(), P.h_lambda.end(), lambda);
+    return P.trace_k ? 1 : 0;
+}
+
+int qe_population_traces(qe_engine* e, int32_t* states, int32_t* actions, double* values) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.trace_k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
+    const size_t m = (size_t)P.runs, k = (size_t)P.trace_k;
+    const bool f32 = e->dtype == QE_F32;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hs(m * k), ha(m * k);
+    std::vector<double> he(m * k);
+    HIP_TRY(hipMemcpyAsync(hs.data(), P.trace_s.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), P.trace_a.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(he.data(), P.trace_e.p, m * k * e->esize(), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const float* const he32 = reinterpret_cast<const float*>(he.data());
+    for (size_t r = 0; r < m; ++r)  // [slot][run] -> [run][slot]; free slots read (0, 0, 0.0)
+        for (size_t i = 0; i < k; ++i) {
+            const double v = f32 ? (double)he32[i * m + r] : he[i * m + r];
+            const bool live = v != 0.0;
+            if (states) states[r * k + i] = live ? hs[i * m + r] : 0;
+            if (actions) actions[r * k + i] = live ? ha[i * m + r] : 0;
+            if (values) values[r * k + i] = live ? v : 0.0;
+        }
+    return QE_OK;
+}
+
+int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int32_t* actions, const double* values) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.trace_k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!states && !actions && !values) return traces_clear(e);
+    if (!states || !actions || !values) return qe_fail(QE_ERR_INVALID, "states, actions or values is NULL");
+    const size_t m = (size_t)P.runs, k = (size_t)P.trace_k;
+    const bool f32 = e->dtype == QE_F32;
+    std::vector<int32_t> hs(m * k, 0), ha(m * k, 0);
+    std::vector<double> he(m * k, 0.0);
+    float* const he32 = reinterpret_cast<float*>(he.data());
+    for (size_t r = 0; r < m; ++r)  // (the kernel indexes the run's table with the live slots)
+        for (size_t i = 0; i < k; ++i) {
+            const double v = values[r * k + i];
+            if (!(v >= 0.0) || std::isinf(v) || (f32 && (double)(float)v != v))
+                return qe_fail(QE_ERR_INVALID, "trace slot %d of run %lld: the value %g is negative, not finite or not a %s",
+                               (int)i, (long long)r, v, f32 ? "float32" : "float64");
+            if (v == 0.0) continue;  // free
+            const int32_t s = states[r * k + i], a = actions[r * k + i];
+            if (s < 0 || s >= P.S)
+                return qe_fail(QE_ERR_INVALID, "trace slot %d of run %lld: state %d is outside [0, %lld)", (int)i, (long long)r, (int)s,
+                               (long long)P.S);
+            if (a < 0 || a >= e->A)
+                return qe_fail(QE_ERR_INVALID, "trace slot %d of run %lld: action %d is outside [0, %d)", (int)i, (long long)r, (int)a,
+                               (int)e->A);
+            for (size_t j = 0; j < i; ++j)
+                if (values[r * k + j] != 0.0 && states[r * k + j] == s && actions[r * k + j] == a)
+                    return qe_fail(QE_ERR_INVALID, "trace slots %d and %d of run %lld name the same cell (%d, %d)", (int)j, (int)i,
+                                   (long long)r, (int)s, (int)a);
+            hs[i * m + r] = s; ha[i * m + r] = a;
+            if (f32) he32[i * m + r] = (float)v;
+            else he[i * m + r] = v;
+        }
+    HIP_TRY(hipMemcpyAsync(P.trace_s.p, hs.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.trace_a.p, ha.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.trace_e.p, he.data(), m * k * e->esize(), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }

@@ -97,7 +97,10 @@ typedef struct qe_rollout_stats {
                                 Q-learning, qe_population_set_double) and path 10: its greedy evaluation, both with
                                 the NV and masked bits of path 6; path 11: population with an n-step on-policy rule
                                 (qe_population_set_n_step): the rule in bits 4-5, NV and masked as path 6, and n in
-                                bits 24-28, which no other path uses */
+                                bits 24-28, which no other path uses; path 12: population with eligibility traces
+                                (qe_population_set_traces): the rule in bits 4-5 (0 = Watkins's Q(lambda), 1 =
+                                SARSA(lambda)), NV and masked as path 6, the slot count K in bits 24-29 and the trace
+                                kind (qe_trace_kind) in bit 30, which no other field of that path uses */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -368,7 +371,32 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         entries at [r * (n - 1) + i], oldest first; unused slots read 0 and are ignored when set.  The
  *                         rollout leaves them behind; set them (len NULL: every window empty, its entries are never
  *                         updated) when the environment state is restored or reset.  A length above n - 1, or a state or
- *                         action outside the table -> QE_ERR_INVALID.  With n = 1 there is nothing to read or set. */
+ *                         action outside the table -> QE_ERR_INVALID.  With n = 1 there is nothing to read or set.
+ *   qe_population_set_traces  eligibility traces (Sutton & Barto ch. 12): SARSA(lambda) under QE_RULE_SARSA, Watkins's
+ *                         Q(lambda) under QE_RULE_Q_LEARNING.  `lambda` has `runs` entries in [0, 1]; NULL turns traces off
+ *                         (the one-step kernels, the default) and frees the slots.  Every run keeps K slots (s_i, a_i, e_i),
+ *                         K in 1 .. 32, e_i of the table dtype T; a slot with e_i == 0 is free and live slots name distinct
+ *                         cells.  A step computes the one-step rule's increment u of Q[s, a] without storing the cell,
+ *                         marks (s, a) -- e = 1 (QE_TRACE_REPLACING) or e + 1 (QE_TRACE_ACCUMULATING) if a live slot holds
+ *                         it, else the lowest free slot, else the slot of the smallest e (lowest index among equals) takes
+ *                         (s, a, 1) -- then adds u * e_i to the cell of every live slot (one product and one add in T; vec
+ *                         mode on a float32 table: in float64, rounded once) and decays: e_i = 0 after a terminated step,
+ *                         else e_i = T(e_i * d) with d = T(gamma * lambda), one float64 product rounded once.  Q(lambda)
+ *                         zeroes every e_i before the mark when the action taken is not a greedy one (Q[s, a] != max Q[s,
+ *                         valid]).  Setting traces frees every slot.  Not a population engine, K or kind out of range ->
+ *                         QE_ERR_INVALID; the rule is Expected SARSA, the double switch is on, n > 1, a lambda outside
+ *                         [0, 1] or not finite, or a d outside [0, 1] -> QE_ERR_UNSUPPORTED, and so is switching to Expected
+ *                         SARSA, the double estimator or n > 1 while traces are on.  Greedy evaluation neither reads nor
+ *                         clears the slots.
+ *   qe_population_trace_config  returns 1 while traces are on, else 0 (or a negative qe_status); K (0 while off), the
+ *                         kind and the `runs` lambdas go to the pointers that are not NULL.
+ *   qe_population_traces / qe_population_set_trace_state  the slots, run state besides the tables and the pending
+ *                         actions: runs * K entries each, run r's slot i at [r * K + i], values as float64 (exact for
+ *                         either dtype); free slots read (0, 0, 0.0).  The rollout leaves them behind; set them (all three
+ *                         NULL: every slot free) when the environment state is restored or reset.  QE_ERR_INVALID while
+ *                         traces are off, and from the setter for a state or action outside the table, a value that is
+ *                         negative, not finite or not representable in T, or two live slots of one run naming one cell. */
+enum qe_trace_kind { QE_TRACE_REPLACING = 0, QE_TRACE_ACCUMULATING = 1 };
 enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
 typedef struct qe_run_schedule {
@@ -405,6 +433,10 @@ int qe_population_n_step(qe_engine* e);
 int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards);
 int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
                              const float* rewards);
+int qe_population_set_traces(qe_engine* e, int32_t trace_length, int32_t trace_kind, const double* lambda);
+int qe_population_trace_config(qe_engine* e, int32_t* trace_length, int32_t* trace_kind, double* lambda);
+int qe_population_traces(qe_engine* e, int32_t* states, int32_t* actions, double* values);
+int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int32_t* actions, const double* values);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

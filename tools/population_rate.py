@@ -3,6 +3,7 @@ rollout on the same environment, measured in the same process.
 
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
                                     [--rule q_learning|sarsa|expected_sarsa] [--n-step N] [--double] [--actions A]
+                                    [--trace-decay LAMBDA [--trace-length K] [--trace-kind replacing|accumulating]]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
@@ -14,6 +15,9 @@ run it under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/populati
 the Q-learning one-agent rollout) and writes DIR/population_rate_<rule>.json for a rule other than q_learning.
 --n-step N (2 .. 16, with --rule sarsa / expected_sarsa) trains with the n-step form of the rule (k_nstep_rollout) and
 writes DIR/population_rate_<rule>_n<N>.json.
+--trace-decay LAMBDA (with --rule q_learning / sarsa) trains with eligibility traces (k_trace_rollout: Watkins's
+Q(lambda) / SARSA(lambda)) of --trace-length K slots (default 16) and --trace-kind (default replacing), and writes
+DIR/population_rate_<rule>_trace<K>.json.
 --double trains (or, with --evaluate, evaluates) a Double Q-learning population (double_q=True: k_double_rollout /
 k_double_evaluate, two tables per run) against the same single-table standalone baseline and writes
 DIR/population_rate_double.json (DIR/population_eval_rate_double.json).
@@ -73,13 +77,15 @@ def schedules():
     return ExponentialSchedule(0.1, 1e-3, 0.9995), ExponentialSchedule(1.0, 0.05, 0.9995)
 
 
-def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1):
+def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1, traces=None):
     lr, eps = schedules()
     kw = {} if rule == "q_learning" else {"update_rule": rule}
     if n_step != 1:
         kw["n_step"] = n_step
     if double_q:
         kw["double_q"] = True
+    if traces is not None:
+        kw.update(trace_decay=traces[0], trace_length=traces[1], trace_kind=traces[2])
     pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
@@ -143,6 +149,9 @@ def main() -> None:
                     help="update rule of the trained population (not with --evaluate: evaluation does not depend on it)")
     ap.add_argument("--n-step", type=int, default=1, help="bootstrapping horizon of the on-policy rules (1 .. 16)")
     ap.add_argument("--double", action="store_true", help="Double Q-learning: two tables per run (q_learning only)")
+    ap.add_argument("--trace-decay", type=float, default=None, help="lambda of the eligibility traces (default: none)")
+    ap.add_argument("--trace-length", type=int, default=16, help="trace slots per run (1 .. 32)")
+    ap.add_argument("--trace-kind", choices=["replacing", "accumulating"], default="replacing")
     ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
     if args.evaluate and args.rule != "q_learning":
@@ -151,6 +160,9 @@ def main() -> None:
         ap.error("--double is Double Q-learning: it goes with --rule q_learning")
     if args.n_step != 1 and (args.rule == "q_learning" or args.evaluate):
         ap.error("--n-step goes with --rule sarsa or expected_sarsa (training runs)")
+    if args.trace_decay is not None and (args.rule == "expected_sarsa" or args.double or args.n_step != 1 or args.evaluate):
+        ap.error("--trace-decay goes with --rule q_learning or sarsa (training runs), without --double and --n-step")
+    traces = None if args.trace_decay is None else (args.trace_decay, args.trace_length, args.trace_kind)
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
     P, isd = frozen_lake_8x8_slippery()
@@ -178,9 +190,9 @@ def main() -> None:
         if args.evaluate:
             pop = population_eval_rate(make_env, M, S, A, k, dtype, log, args.double)
         else:
-            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step)
+            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step, traces)
         base = base_cache[name]
-        line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, **({"n_step": args.n_step} if args.n_step != 1 else {}), **({"double": True} if args.double else {}), "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
+        line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, **({"n_step": args.n_step} if args.n_step != 1 else {}), **({"trace_decay": traces[0], "trace_length": traces[1], "trace_kind": traces[2]} if traces else {}), **({"double": True} if args.double else {}), "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
                 "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
         lines.append(line)
         print(f"{name:14s} M={M:6d} log={int(log)} {pop['env_steps_per_s'] / 1e6:10.1f} M env-steps/s "
@@ -190,6 +202,8 @@ def main() -> None:
     name = "population_eval_rate.json" if args.evaluate else "population_rate.json"
     if args.rule != "q_learning":
         name = f"population_rate_{args.rule}.json" if args.n_step == 1 else f"population_rate_{args.rule}_n{args.n_step}.json"
+    if traces:
+        name = f"population_rate_{args.rule}_trace{args.trace_length}.json"
     if args.double:
         name = name.replace(".json", "_double.json")
     (args.out / name).write_text(json.dumps(lines, indent=1))
