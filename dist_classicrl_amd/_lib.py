@@ -36,6 +36,7 @@ PATH_AUTO, PATH_STEPWISE, PATH_PERSISTENT, PATH_WIDE, PATH_TURNSTILE = 0, 1, 2, 
 RULE_Q_LEARNING, RULE_SARSA, RULE_EXPECTED_SARSA = 0, 1, 2  # qe_update_rule
 N_STEP_MAX = 16  # qe_population_set_n_step
 TRACE_MAX = 32  # qe_population_set_traces
+PLANNING_MAX = 64  # qe_population_set_planning
 TRACE_REPLACING, TRACE_ACCUMULATING = 0, 1  # qe_trace_kind
 TRACE_KINDS = {"replacing": TRACE_REPLACING, "accumulating": TRACE_ACCUMULATING}
 UPDATE_RULES = {"q_learning": RULE_Q_LEARNING, "sarsa": RULE_SARSA, "expected_sarsa": RULE_EXPECTED_SARSA}
@@ -52,15 +53,16 @@ def decode_variant(v: int) -> dict:
     bits 4-5 as path 8, and ``n_step`` in bits 24-28 (1 on every other path).  Path 12 (``population_trace``, kernel
     ``k_trace_rollout``) is the population with eligibility traces: the rule in bits 4-5 (0 = Q-learning, Watkins's
     Q(lambda); 1 = SARSA(lambda)), ``trace_length`` in bits 24-29 and ``trace_kind`` in bit 30 (0 and None on every other
-    path)."""
+    path).  Path 13 (``population_dyna``, kernel ``k_dyna_rollout``) is the Q-learning population with Dyna-Q: NV and
+    masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has."""
     v = int(v)
     nstep = (v & 15) == 11
     trace = (v & 15) == 12
     td = (v & 15) == 8 or nstep
-    return {
+    out = {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
                  7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval",
-                 11: "population_nstep", 12: "population_trace"}.get(v & 15, "none"),
+                 11: "population_nstep", 12: "population_trace", 13: "population_dyna"}.get(v & 15, "none"),
         "rule": ({1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td
                  else {0: "q_learning", 1: "sarsa"}.get((v >> 4) & 3, "none") if trace else "q_learning"),
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
@@ -69,6 +71,9 @@ def decode_variant(v: int) -> dict:
         "trace_length": (v >> 24) & 63 if trace else 0,
         "trace_kind": ("accumulating" if (v >> 30) & 1 else "replacing") if trace else None,
     }
+    if (v & 15) == 13:
+        out["planning_steps"] = (v >> 24) & 127
+    return out
 
 
 def variant_symbol(v: int, dtype: str = "float", env: str = "HashEnv", lanes_per_row: int = 4, vec: bool = False) -> str:
@@ -229,6 +234,10 @@ PROTOTYPES = {
     "qe_population_trace_config": (C.c_int, [_P, _I32P, _I32P, _F64P]),
     "qe_population_traces": (C.c_int, [_P, _I32P, _I32P, _F64P]),
     "qe_population_set_trace_state": (C.c_int, [_P, _I32P, _I32P, _F64P]),
+    "qe_population_set_planning": (C.c_int, [_P, C.c_int32]),
+    "qe_population_planning": (C.c_int, [_P]),
+    "qe_population_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
+    "qe_population_set_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_debug_set_turn_epoch": (C.c_int, [_P, C.c_uint64]),
     "qe_debug_turn_epoch": (C.c_uint64, [_P]),

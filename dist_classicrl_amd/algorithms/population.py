@@ -47,6 +47,16 @@ the one-step rule's increment, and decays every trace by ``gamma * lam``; Q(lamb
 action.  ``state_dict["eligibility_traces"]`` carries the slots from call to call.  ``update_rule="expected_sarsa"``,
 ``double_q=True`` and ``n_step > 1`` are refused with traces.  DESIGN section 4.3c defines the step;
 ``tests/trace_model.py`` restates it on the oracle.
+
+``planning_steps=n`` (0 .. 64, Q-learning only; kernel ``k_dyna_rollout``) turns on Dyna-Q (Sutton & Barto ch. 8), the
+model-based method: every run remembers the last observed outcome ``(s', r, terminated)`` of every cell it has tried
+and, after each real step, replays ``n`` remembered transitions, drawn from the cells it has seen, through the same
+Q-learning update -- on sparse-reward tasks the largest lever on sample efficiency a tabular learner has.  The model is
+knowledge, like the tables: it outlives calls and environment resets, greedy evaluation neither reads nor writes it, and
+it is NOT in the state dict.  :attr:`planning_model` reads and sets it, ``save_model`` / ``load_model`` keep it in one
+``.npz``.  A fresh process resumes with ``load`` (tables), ``load_model`` (model) and ``restore_training_state`` (counters,
+schedules), then passes the state dict to ``run_steps``.  ``double_q=True``, ``n_step > 1`` and ``trace_decay`` are
+refused with planning.  DESIGN section 4.3c defines the step; ``tests/dyna_model.py`` restates it on the oracle.
 """
 
 from __future__ import annotations
@@ -195,6 +205,34 @@ def trace_arrays(traces, runs, trace_length) -> tuple | None:
     return tuple(out)
 
 
+def model_arrays(model, runs, state_size, action_size) -> tuple | None:
+    """A ``planning_model`` as the ``(next_states, rewards, terminated, visited, count)`` arrays the library takes (None:
+    nothing is known): int32 ``[runs, S, A]``, float32 ``[runs, S, A]``, uint8 ``[runs, S, A]``, int32 ``[runs, S * A]`` and
+    int32 ``[runs]``; ``ValueError`` on anything else.  Whether list and model agree is the library's check."""
+    if model is None:
+        return None
+    keys = ["count", "next_states", "rewards", "terminated", "visited"]
+    if not isinstance(model, dict) or sorted(model) != keys:
+        msg = "planning_model: expected a dict with the keys 'next_states', 'rewards', 'terminated', 'visited' and 'count'"
+        raise ValueError(msg)
+    cells = (runs, state_size, action_size)
+    out = []
+    for key, shape, kinds, dtype in (("next_states", cells, "iu", np.int32), ("rewards", cells, "f", np.float32),
+                                     ("terminated", cells, "b", np.uint8), ("visited", (runs, state_size * action_size), "iu", np.int32),
+                                     ("count", (runs,), "iu", np.int32)):
+        arr = np.asarray(model[key])
+        if arr.shape != shape or arr.dtype.kind not in kinds or (key == "rewards" and arr.dtype.itemsize > 4
+                                                                 and not np.array_equal(arr.astype(np.float32), arr, equal_nan=True)):
+            want = "bool" if key == "terminated" else np.dtype(dtype)
+            msg = f"planning_model[{key!r}]: expected shape {shape} of {want}, got shape {arr.shape} of {arr.dtype}"
+            raise ValueError(msg)
+        if kinds == "iu" and arr.size and (arr.min() < -(2 ** 31) or arr.max() >= 2 ** 31):
+            msg = f"planning_model[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got values outside int32"
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(arr, dtype=dtype))
+    return tuple(out)
+
+
 def _per_run(value, runs, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != runs:
@@ -212,13 +250,14 @@ class QLearningPopulation:
     run, Q-learning only) and ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) hold for all of them.
     ``trace_decay`` (None: no traces; else one lambda in [0, 1] or a sequence of ``runs``) turns on eligibility traces for
     "sarsa" and "q_learning", with ``trace_length`` slots per run (1 .. 32) of ``trace_kind`` "replacing" or
-    "accumulating".  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    "accumulating".  ``planning_steps`` (0: none; 1 .. 64) turns on Dyna-Q for "q_learning": that many planning updates
+    from the run's learned model after every step (:attr:`planning_model`).  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
                  update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
-                 trace_kind="replacing"):
+                 trace_kind="replacing", planning_steps=0):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -248,6 +287,28 @@ class QLearningPopulation:
             msg = (f"n_step={n_step} needs update_rule='sarsa' or 'expected_sarsa': an uncorrected n-step Q-learning is not an "
                    "off-policy method (importance sampling and tree backup are not built)")
             raise ValueError(msg)
+        if (isinstance(planning_steps, (bool, np.bool_)) or not isinstance(planning_steps, (int, np.integer))
+                or not 0 <= planning_steps <= _lib.PLANNING_MAX):
+            msg = f"planning_steps must be an integer in 0 .. {_lib.PLANNING_MAX}, got {planning_steps!r}"
+            raise ValueError(msg)
+        if planning_steps > 0:
+            if update_rule != "q_learning":
+                msg = (f"planning_steps={planning_steps} needs update_rule='q_learning', got {update_rule!r}: Dyna-Q replays "
+                       "remembered transitions through Q-learning's update; planning for the on-policy rules is not built")
+                raise ValueError(msg)
+            if double_q:
+                msg = f"planning_steps={planning_steps} with double_q=True: Dyna-Q plans on one table"
+                raise ValueError(msg)
+            if n_step > 1:
+                msg = f"planning_steps={planning_steps} with n_step={n_step}: Dyna-Q is a one-step method"
+                raise ValueError(msg)
+            if trace_decay is not None:
+                msg = f"planning_steps={planning_steps} with trace_decay: Dyna-Q is a one-step method"
+                raise ValueError(msg)
+            if self.state_size * self.action_size >= 2 ** 31:
+                msg = f"planning_steps={planning_steps}: state_size * action_size must be below 2^31"
+                raise ValueError(msg)
+        self.planning_steps = int(planning_steps)
         self.update_rule = update_rule
         self.double_q = bool(double_q)
         self.n_step = int(n_step)
@@ -316,6 +377,8 @@ class QLearningPopulation:
         if self.trace_decay is not None:
             _lib.check(self._lib.qe_population_set_traces(self._h, self.trace_length, _lib.TRACE_KINDS[self.trace_kind],
                                                           _lib.ptr(self.trace_decay, C.c_double)))
+        if self.planning_steps:
+            _lib.check(self._lib.qe_population_set_planning(self._h, self.planning_steps))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -431,6 +494,54 @@ class QLearningPopulation:
         states, actions, values = arrays
         _lib.check(self._lib.qe_population_set_trace_state(self._h, _lib.ptr(states, C.c_int32), _lib.ptr(actions, C.c_int32),
                                                            _lib.ptr(values, C.c_double)))
+
+    @property
+    def planning_model(self) -> dict | None:
+        """``planning_steps > 0``: what every run has learned about its environment, a dict of ``next_states`` (int32
+        ``[runs, S, A]``, -1: unseen), ``rewards`` (float32, 0 where unseen), ``terminated`` (bool) -- the last observed
+        outcome of every cell --, ``visited`` (int32 ``[runs, S * A]``: the seen cells ``s * A + a`` in order of first
+        observation, -1 past the count) and ``count`` (int32 ``[runs]``).  Without planning: None.  Setting None forgets
+        everything; a dict whose list names an unseen, repeated or out-of-range cell, or whose count differs from the
+        number of seen cells, is a ``ValueError``."""
+        if not self.planning_steps:
+            return None
+        cells = (self.runs, self.state_size, self.action_size)
+        nxt, rew, term = np.empty(cells, dtype=np.int32), np.empty(cells, dtype=np.float32), np.empty(cells, dtype=np.uint8)
+        visited = np.empty((self.runs, self.state_size * self.action_size), dtype=np.int32)
+        count = np.empty(self.runs, dtype=np.int32)
+        _lib.check(self._lib.qe_population_model(self._h, _lib.ptr(nxt, C.c_int32), _lib.ptr(rew, C.c_float), _lib.ptr(term, C.c_uint8),
+                                                 _lib.ptr(visited, C.c_int32), _lib.ptr(count, C.c_int32)))
+        return {"next_states": nxt, "rewards": rew, "terminated": term.astype(bool), "visited": visited, "count": count}
+
+    @planning_model.setter
+    def planning_model(self, model) -> None:
+        if not self.planning_steps:
+            if model is not None:
+                msg = "a population without planning_steps has no planning model"
+                raise ValueError(msg)
+            return
+        arrays = model_arrays(model, self.runs, self.state_size, self.action_size)
+        if arrays is None:
+            _lib.check(self._lib.qe_population_set_model(self._h, None, None, None, None, None))
+            return
+        nxt, rew, term, visited, count = arrays
+        _lib.check(self._lib.qe_population_set_model(self._h, _lib.ptr(nxt, C.c_int32), _lib.ptr(rew, C.c_float),
+                                                     _lib.ptr(term, C.c_uint8), _lib.ptr(visited, C.c_int32),
+                                                     _lib.ptr(count, C.c_int32)))
+
+    def save_model(self, filename) -> None:
+        """:attr:`planning_model` as one ``.npz`` (``ValueError`` without planning)."""
+        model = self.planning_model
+        if model is None:
+            msg = "a population without planning_steps has no planning model"
+            raise ValueError(msg)
+        with open(filename, "wb") as f:  # (an open file: np.savez appends ".npz" to a name that lacks it)
+            np.savez(f, **model)
+
+    def load_model(self, filename) -> None:
+        """What :meth:`save_model` wrote."""
+        with np.load(filename) as z:
+            self.planning_model = {key: z[key] for key in z.files}
 
     def _rng_step(self):
         """``state_dict["rng_step"]``: an int while all runs agree, else the int64 array of every run's."""
@@ -758,4 +869,4 @@ class QLearningPopulation:
 
 
 __all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "pending_array", "schedule_descriptor", "trace_arrays", "window_arrays"]
+           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "window_arrays"]

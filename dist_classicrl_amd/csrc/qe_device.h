@@ -14,6 +14,7 @@ namespace qe {
 
 constexpr uint32_t STREAM_POLICY = 0;
 constexpr uint32_t STREAM_ENV = 1;
+constexpr uint32_t STREAM_PLAN = 2;  // Dyna-Q's planning draws: block b of a step at STREAM_PLAN | b << 8 (qe_rollout_dyna.h)
 
 struct U4 {
     uint32_t x, y, z, w;

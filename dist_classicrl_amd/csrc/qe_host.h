@@ -29,6 +29,7 @@ namespace qe {
 struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
 template <typename T>
 struct TraceSlots;  // the slots of the eligibility traces (qe_rollout_trace.h)
+struct DynaModel;   // the learned model and visited list of Dyna-Q (qe_rollout_dyna.h)
 }
 
 // records the text qe_last_error() returns (thread-local) and hands `code` back
@@ -200,6 +201,13 @@ struct PopState {
     DevBuf<double> trace_e;
     DevBuf<double> trace_lambda;
     std::vector<double> h_lambda;
+    // Dyna-Q (qe_population_set_planning): planning updates per step, 0 = off (the kernels above).  On: every run's
+    // learned model, one 8-byte entry per table cell ([runs][S * ld]: next_obs | terminated << 31 or 0xFFFFFFFF = unseen,
+    // then the reward's bits), the table offsets of its seen cells in order of first observation ([runs][S * A]) and their
+    // count (k_dyna_rollout, qe_rollout_dyna.h); allocated when planning is set, kept until it is set to 0.
+    int planning = 0;
+    DevBuf<uint2> dyna_entry;
+    DevBuf<int32_t> dyna_visited, dyna_count;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
@@ -211,6 +219,8 @@ struct PopState {
         trace_s.release(); trace_a.release(); trace_e.release(); trace_lambda.release();
         h_lambda.clear();
         trace_k = 0;
+        dyna_entry.release(); dyna_visited.release(); dyna_count.release();
+        planning = 0;
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
         off_any = false;
@@ -438,7 +448,8 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   path 11 = population with an n-step on-policy rule (k_nstep_rollout): the rule in bits 4-5, NV and masked as path 6,
 //   and n in bits 24-28, which no other path uses; path 12 = population with eligibility traces (k_trace_rollout): the
 //   rule in bits 4-5 (0 = Watkins's Q(lambda), 1 = SARSA(lambda)), NV and masked as path 6, K in bits 24-29 and the trace
-//   kind in bit 30, which no other field of that path uses
+//   kind in bit 30, which no other field of that path uses; path 13 = population with Dyna-Q (k_dyna_rollout): NV and
+//   masked as path 6, and the planning updates per step in bits 24-30
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -449,6 +460,7 @@ constexpr int64_t QE_VARIANT_RUNS_TD = 8;  // population, SARSA / Expected SARSA
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE = 9;        // population, Double Q-learning (k_double_rollout): NV and masked bits
 constexpr int64_t QE_VARIANT_RUNS_DOUBLE_EVAL = 10;  // ... and its greedy evaluation (k_double_evaluate)
 constexpr int64_t QE_VARIANT_RUNS_NSTEP = 11;  // population, n-step SARSA / Expected SARSA (k_nstep_rollout): as path 8, + n in bits 24-28
+constexpr int64_t QE_VARIANT_RUNS_DYNA = 13;   // population, Dyna-Q (k_dyna_rollout): NV and masked bits, + planning updates in bits 24-30
 constexpr int64_t QE_VARIANT_RUNS_TRACE = 12;  // population, SARSA(lambda) / Watkins's Q(lambda) (k_trace_rollout): + K in bits 24-29, kind in bit 30
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
@@ -458,7 +470,7 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
-// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip, qe_inst_runs_trace.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip, qe_inst_runs_trace.hip, qe_inst_runs_dyna.hip): go(integral_constant<int, NV>, bool_constant<masked>).
 template <class Env, class F>
 inline int64_t runs_by_build(int ld, bool masked, F go) {
     using Yes = std::true_type;
@@ -495,6 +507,10 @@ int64_t launch_nstep_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx&
 template <typename T, class Env>
 int64_t launch_trace_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
                           int32_t* pending, const TraceSlots<T>& w);
+// ... with Dyna-Q: Q-learning's step, then w.n planning updates from the runs' learned models (qe_inst_runs_dyna.hip)
+template <typename T, class Env>
+int64_t launch_dyna_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
+                         const DynaModel& w);
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
 int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,

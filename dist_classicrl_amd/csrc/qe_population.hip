@@ -8,8 +8,11 @@
 // on-policy rules train through k_nstep_rollout (qe_rollout_nstep.h, instantiated in qe_inst_runs_nstep.hip), which
 // carries every run's window of transitions from launch to launch in the win_* arrays.  With eligibility traces on
 // (qe_population_set_traces) SARSA and Q-learning train through k_trace_rollout (qe_rollout_trace.h, instantiated in
-// qe_inst_runs_trace.hip), which carries every run's trace slots from launch to launch in the trace_* arrays.
+// qe_inst_runs_trace.hip), which carries every run's trace slots from launch to launch in the trace_* arrays.  With
+// planning on (qe_population_set_planning) Q-learning trains through k_dyna_rollout (qe_rollout_dyna.h, instantiated in
+// qe_inst_runs_dyna.hip), which keeps every run's learned model and visited list in the dyna_* arrays.
 #include "qe_host.h"
+#include "qe_rollout_dyna.h"
 #include "qe_rollout_nstep.h"
 #include "qe_rollout_trace.h"
 
@@ -77,9 +80,10 @@ int need_population(const qe_engine* e) {
     return QE_OK;
 }
 
-// Steps per launch of a call of `steps` steps of M runs (the budgets above).
-long long launch_len(int64_t M, int64_t steps, bool log) {
-    long long per_launch = std::max<long long>(1, RUNS_STEP_BUDGET / M);
+// Steps per launch of a call of `steps` steps of M runs (the budgets above).  `planning`: table updates a step makes
+// beside its own (Dyna-Q), which share the step budget -- a launch holds the device no longer with them than without.
+long long launch_len(int64_t M, int64_t steps, bool log, int planning = 0) {
+    long long per_launch = std::max<long long>(1, RUNS_STEP_BUDGET / M / (1 + planning));
     if (log) per_launch = std::min<long long>(per_launch, std::max<long long>(1, RUNS_LOG_BUDGET / M));
     if (steps > 0) per_launch = std::min<long long>(per_launch, steps);
     return per_launch;
@@ -236,6 +240,16 @@ int traces_clear(qe_engine* e) {
     return QE_OK;
 }
 
+// Dyna-Q: every run's model unseen, its list empty.
+int model_clear(qe_engine* e) {
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    HIP_TRY(hipMemsetAsync(P.dyna_entry.p, 0xFF, m * (size_t)P.S * (size_t)e->ld * sizeof(uint2), e->stream));  // DYNA_UNSEEN
+    HIP_TRY(hipMemsetAsync(P.dyna_count.p, 0, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 // The double estimator's table entry points: the qe_table_* call `f` with table B standing in for the engine's table.
 template <class F>
 int on_table_b(qe_engine* e, F f) {
@@ -338,7 +352,7 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
     HIP_TRY(hipSetDevice(e->device));
     const int64_t M = P.runs;
     const size_t m = (size_t)M;
-    const long long per_launch = launch_len(M, steps, log != 0);
+    const long long per_launch = launch_len(M, steps, log != 0, P.planning);
     if (log)
         if (int rc = log_reserve(P, m, per_launch)) return rc;
     env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
@@ -372,6 +386,10 @@ int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t 
                 c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
                 c.step_off = P.off_any ? P.step_off.p : nullptr;
                 if (P.table_b) return launch_double_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, (T*)P.table_b);
+                if (P.planning) {
+                    const DynaModel w{P.planning, P.dyna_entry.p, P.dyna_visited.p, P.dyna_count.p, P.S * (int64_t)e->A};
+                    return launch_dyna_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, w);
+                }
                 if (P.trace_k) {
                     const TraceSlots<T> w{P.trace_k, P.trace_kind, P.trace_s.p, P.trace_a.p, (T*)P.trace_e.p, P.trace_lambda.p};
                     return launch_trace_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
@@ -560,6 +578,11 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
                        "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (importance sampling and "
                        "tree backup are not built); the n-step rules are SARSA and Expected SARSA",
                        e->pop.n_step);
+    if (e->pop.planning && rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "planning is on (%d updates per step): Dyna-Q replays remembered transitions through Q-learning's update; "
+                       "planning for the on-policy rules is not built (qe_population_set_planning)",
+                       e->pop.planning);
     if (e->pop.trace_k && rule == QE_RULE_EXPECTED_SARSA)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "eligibility traces are on: the trace form of Expected SARSA needs policy-probability weighting, which "
@@ -580,6 +603,8 @@ int qe_population_set_double(qe_engine* e, int32_t on) {
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.n_step);
     if (on && P.trace_k)
         return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces are on: the double estimator has no trace form (qe_population_set_traces)");
+    if (on && P.planning)
+        return qe_fail(QE_ERR_UNSUPPORTED, "planning is on: Dyna-Q plans on one table (qe_population_set_planning)");
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", P.rule);
     HIP_TRY(hipSetDevice(e->device));
@@ -674,6 +699,8 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
                        (int)n);
     if (n > 1 && P.table_b)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
+    if (n > 1 && P.planning)
+        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)", (int)n);
     if (n > 1 && P.trace_k)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
     if (n == P.n_step) return QE_OK;
@@ -780,6 +807,8 @@ int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double
                        "eligibility traces with Expected SARSA: its trace form needs policy-probability weighting, which is not "
                        "built; the trace rules are SARSA and Q-learning");
     if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces: the double estimator has no trace form (qe_population_set_double)");
+    if (P.planning)
+        return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)");
     if (P.n_step > 1)
         return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces with n_step = %d: one multi-step method at a time (qe_population_set_n_step)", P.n_step);
     HIP_TRY(hipSetDevice(e->device));
@@ -868,6 +897,149 @@ int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int
     HIP_TRY(hipMemcpyAsync(P.trace_s.p, hs.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(P.trace_a.p, ha.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(P.trace_e.p, he.data(), m * k * e->esize(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_set_planning(qe_engine* e, int32_t n) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (n < 0 || n > DYNA_MAX) return qe_fail(QE_ERR_INVALID, "planning_steps must be in 0 .. %d, got %d", DYNA_MAX, (int)n);
+    if (n == 0) {  // off: the model is forgotten
+        if (!P.planning) return QE_OK;
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        P.dyna_entry.release(); P.dyna_visited.release(); P.dyna_count.release();
+        P.planning = 0;
+        return QE_OK;
+    }
+    if (P.rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "planning with update rule %d: Dyna-Q replays remembered transitions through Q-learning's update; planning "
+                       "for the on-policy rules is not built",
+                       P.rule);
+    if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "planning: Dyna-Q plans on one table, the double estimator has two (qe_population_set_double)");
+    if (P.n_step > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "planning with n_step = %d: Dyna-Q is a one-step method (qe_population_set_n_step)", P.n_step);
+    if (P.trace_k) return qe_fail(QE_ERR_UNSUPPORTED, "planning with eligibility traces: Dyna-Q is a one-step method (qe_population_set_traces)");
+    // (the list and the kernel name a cell by its offset in the run's table, an int32; ld >= A)
+    if ((double)P.S * (double)e->ld >= 2147483648.0)
+        return qe_fail(QE_ERR_UNSUPPORTED, "planning: a run's table must hold fewer than 2^31 cells (state_size * row stride = %lld * %d)",
+                       (long long)P.S, (int)e->ld);
+    if (P.planning) {  // already on: the model is knowledge and stays
+        P.planning = n;
+        return QE_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t m = (size_t)P.runs;
+    hipError_t err = P.dyna_entry.ensure(m * (size_t)P.S * (size_t)e->ld);
+    if (err == hipSuccess) err = P.dyna_visited.ensure(m * (size_t)P.S * (size_t)e->A);
+    if (err == hipSuccess) err = P.dyna_count.ensure(m);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        P.dyna_entry.release(); P.dyna_visited.release(); P.dyna_count.release();
+        return qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "planning: the model could not be allocated: %s",
+                       hipGetErrorString(err));
+    }
+    if (int rc = model_clear(e)) return rc;
+    P.planning = n;
+    return QE_OK;
+}
+
+int qe_population_planning(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    return e->pop.planning;
+}
+
+int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint8_t* terminated, int32_t* visited, int32_t* count) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hc(m);
+    HIP_TRY(hipMemcpyAsync(hc.data(), P.dyna_count.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (next_states || rewards || terminated) {
+        std::vector<uint2> he(m * S * ld);
+        HIP_TRY(hipMemcpyAsync(he.data(), P.dyna_entry.p, he.size() * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t r = 0; r < m; ++r)
+            for (size_t s = 0; s < S; ++s)
+                for (size_t a = 0; a < A; ++a) {
+                    const uint2 x = he[(r * S + s) * ld + a];
+                    const bool seen = x.x != DYNA_UNSEEN;
+                    const size_t at = (r * S + s) * A + a;
+                    if (next_states) next_states[at] = seen ? (int32_t)(x.x & 0x7FFFFFFFu) : -1;
+                    if (rewards) {
+                        const uint32_t bits = seen ? x.y : 0u;
+                        memcpy(&rewards[at], &bits, sizeof bits);
+                    }
+                    if (terminated) terminated[at] = seen && (x.x >> 31) ? 1 : 0;
+                }
+    }
+    if (visited) {
+        std::vector<int32_t> hv(m * S * A);
+        HIP_TRY(hipMemcpyAsync(hv.data(), P.dyna_visited.p, hv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t r = 0; r < m; ++r)  // table offsets s * ld + a -> cells s * A + a; -1 past the count
+            for (size_t j = 0; j < S * A; ++j) {
+                const int32_t o = hv[r * S * A + j];
+                visited[r * S * A + j] = j < (size_t)hc[r] ? (int32_t)((size_t)o / ld * A + (size_t)o % ld) : -1;
+            }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (count) std::copy(hc.begin(), hc.end(), count);
+    return QE_OK;
+}
+
+int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
+                            const int32_t* visited, const int32_t* count) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!next_states && !rewards && !terminated && !visited && !count) return model_clear(e);
+    if (!next_states || !rewards || !terminated || !visited || !count)
+        return qe_fail(QE_ERR_INVALID, "next_states, rewards, terminated, visited or count is NULL");
+    const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    std::vector<uint2> he(m * S * ld, make_uint2(DYNA_UNSEEN, DYNA_UNSEEN));
+    std::vector<int32_t> hv(m * S * A, 0);
+    std::vector<uint8_t> listed(S * A);
+    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes the run's table with the entries and the list)
+        size_t seen = 0;
+        for (size_t c = 0; c < S * A; ++c) {
+            const int32_t p = next_states[r * S * A + c];
+            if (p == -1) continue;
+            if (p < 0 || (size_t)p >= S)
+                return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld: next state %d is outside [0, %lld) and is not -1",
+                               (long long)r, (long long)c, (int)p, (long long)S);
+            uint32_t bits;
+            memcpy(&bits, &rewards[r * S * A + c], sizeof bits);
+            he[(r * S + c / A) * ld + c % A] = make_uint2((uint32_t)p | (terminated[r * S * A + c] ? 0x80000000u : 0u), bits);
+            ++seen;
+        }
+        if (count[r] < 0 || (size_t)count[r] != seen)
+            return qe_fail(QE_ERR_INVALID, "model of run %lld: count is %d, the model holds %lld seen cells", (long long)r, (int)count[r],
+                           (long long)seen);
+        std::fill(listed.begin(), listed.end(), 0);
+        for (size_t j = 0; j < seen; ++j) {
+            const int32_t c = visited[r * S * A + j];
+            if (c < 0 || (size_t)c >= S * A)
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is outside [0, %lld)", (long long)r,
+                               (long long)j, (int)c, (long long)(S * A));
+            if (next_states[r * S * A + (size_t)c] == -1)
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is unseen in the model", (long long)r,
+                               (long long)j, (int)c);
+            if (listed[(size_t)c])
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is listed twice", (long long)r, (long long)j,
+                               (int)c);
+            listed[(size_t)c] = 1;
+            hv[r * S * A + j] = (int32_t)((size_t)c / A * ld + (size_t)c % A);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(P.dyna_entry.p, he.data(), he.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna_visited.p, hv.data(), hv.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna_count.p, count, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }

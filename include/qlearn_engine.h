@@ -100,7 +100,9 @@ typedef struct qe_rollout_stats {
                                 bits 24-28, which no other path uses; path 12: population with eligibility traces
                                 (qe_population_set_traces): the rule in bits 4-5 (0 = Watkins's Q(lambda), 1 =
                                 SARSA(lambda)), NV and masked as path 6, the slot count K in bits 24-29 and the trace
-                                kind (qe_trace_kind) in bit 30, which no other field of that path uses */
+                                kind (qe_trace_kind) in bit 30, which no other field of that path uses; path 13:
+                                population with Dyna-Q (qe_population_set_planning): NV and masked as path 6, and the
+                                planning updates per step in bits 24-30 */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -395,7 +397,32 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         either dtype); free slots read (0, 0, 0.0).  The rollout leaves them behind; set them (all three
  *                         NULL: every slot free) when the environment state is restored or reset.  QE_ERR_INVALID while
  *                         traces are off, and from the setter for a state or action outside the table, a value that is
- *                         negative, not finite or not representable in T, or two live slots of one run naming one cell. */
+ *                         negative, not finite or not representable in T, or two live slots of one run naming one cell.
+ *   qe_population_set_planning  Dyna-Q (Sutton & Barto ch. 8): n planning updates after every training step, n in 0 .. 64;
+ *                         0 (the default) turns planning off and forgets the model.  Every run keeps a model -- for every
+ *                         cell c = s * A + a its last observed outcome (next_obs, reward, terminated), or "unseen" -- and
+ *                         the list of its seen cells in order of first observation.  A step with draw counter k is
+ *                         Q-learning's step; then model[s, a] = (s', r, terminated), s' the observation the environment
+ *                         returns (an unseen cell joins the list first); then, for i = 0 .. n-1 in order: x_i = word i & 3
+ *                         of the Philox block (agent id, k_lo, k_hi, 2 | (i >> 2) << 8) under the engine's seed,
+ *                         c_i = list[mulhi32(x_i, count)], (p, rho, tau) = model[c_i], m_i = the maximum of row p over the
+ *                         environment's valid columns for observation p as the table stands then (a NaN there: NaN; no
+ *                         valid column: -inf) and Q[c_i] = the step's update of (Q[c_i], rho, m_i, tau) with the learning
+ *                         rate of step k.  The model outlives calls and environment resets; greedy evaluation neither
+ *                         reads nor writes it.  Setting n > 0 while planning is on keeps the model.  Not a population
+ *                         engine or n out of range -> QE_ERR_INVALID; a rule other than Q-learning, the double switch on,
+ *                         n_step > 1, traces on, or a run's table of 2^31 cells or more (state_size * row stride) ->
+ *                         QE_ERR_UNSUPPORTED, and so is switching to any of those while planning is on.
+ *   qe_population_planning  n, 0 while planning is off (or a negative qe_status).
+ *   qe_population_model / qe_population_set_model  the model and the list: next_states (-1: unseen), rewards and
+ *                         terminated hold runs * S * A entries, run r's cell c at [r * S * A + c]; visited holds
+ *                         runs * S * A cells, run r's j-th at [r * S * A + j], -1 from count[r] on; count holds runs
+ *                         entries.  The download fills the pointers that are not NULL (unseen cells read -1, 0.0f, 0).
+ *                         The upload takes all five, or all NULL: every run forgets everything.  QE_ERR_INVALID while
+ *                         planning is off, and from the upload for a next state outside [0, S) that is not -1, a count
+ *                         that differs from the number of seen cells, or a list entry (below count) that is out of range,
+ *                         unseen in the model or listed twice; entries from count on and the rewards and flags of unseen
+ *                         cells are not read. */
 enum qe_trace_kind { QE_TRACE_REPLACING = 0, QE_TRACE_ACCUMULATING = 1 };
 enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
@@ -437,6 +464,12 @@ int qe_population_set_traces(qe_engine* e, int32_t trace_length, int32_t trace_k
 int qe_population_trace_config(qe_engine* e, int32_t* trace_length, int32_t* trace_kind, double* lambda);
 int qe_population_traces(qe_engine* e, int32_t* states, int32_t* actions, double* values);
 int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int32_t* actions, const double* values);
+int qe_population_set_planning(qe_engine* e, int32_t planning_steps);
+int qe_population_planning(qe_engine* e);
+int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint8_t* terminated, int32_t* visited,
+                        int32_t* count);
+int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
+                            const int32_t* visited, const int32_t* count);
 
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its

@@ -4,6 +4,7 @@ rollout on the same environment, measured in the same process.
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
                                     [--rule q_learning|sarsa|expected_sarsa] [--n-step N] [--double] [--actions A]
                                     [--trace-decay LAMBDA [--trace-length K] [--trace-kind replacing|accumulating]]
+                                    [--planning-steps N]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
@@ -18,6 +19,9 @@ writes DIR/population_rate_<rule>_n<N>.json.
 --trace-decay LAMBDA (with --rule q_learning / sarsa) trains with eligibility traces (k_trace_rollout: Watkins's
 Q(lambda) / SARSA(lambda)) of --trace-length K slots (default 16) and --trace-kind (default replacing), and writes
 DIR/population_rate_<rule>_trace<K>.json.
+--planning-steps N (1 .. 64, with --rule q_learning) trains with Dyna-Q (k_dyna_rollout): N planning updates from the
+run's learned model after every step; writes DIR/population_rate_dyna<N>.json, with the event time per table update
+(env-step time / (1 + N)) beside the time per env-step.
 --double trains (or, with --evaluate, evaluates) a Double Q-learning population (double_q=True: k_double_rollout /
 k_double_evaluate, two tables per run) against the same single-table standalone baseline and writes
 DIR/population_rate_double.json (DIR/population_eval_rate_double.json).
@@ -77,7 +81,8 @@ def schedules():
     return ExponentialSchedule(0.1, 1e-3, 0.9995), ExponentialSchedule(1.0, 0.05, 0.9995)
 
 
-def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1, traces=None):
+def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1, traces=None,
+                    planning=0):
     lr, eps = schedules()
     kw = {} if rule == "q_learning" else {"update_rule": rule}
     if n_step != 1:
@@ -86,6 +91,8 @@ def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", dou
         kw["double_q"] = True
     if traces is not None:
         kw.update(trace_decay=traces[0], trace_length=traces[1], trace_kind=traces[2])
+    if planning:
+        kw["planning_steps"] = planning
     pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
@@ -152,6 +159,7 @@ def main() -> None:
     ap.add_argument("--trace-decay", type=float, default=None, help="lambda of the eligibility traces (default: none)")
     ap.add_argument("--trace-length", type=int, default=16, help="trace slots per run (1 .. 32)")
     ap.add_argument("--trace-kind", choices=["replacing", "accumulating"], default="replacing")
+    ap.add_argument("--planning-steps", type=int, default=0, help="Dyna-Q planning updates per step (0 .. 64; q_learning only)")
     ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
     if args.evaluate and args.rule != "q_learning":
@@ -162,6 +170,9 @@ def main() -> None:
         ap.error("--n-step goes with --rule sarsa or expected_sarsa (training runs)")
     if args.trace_decay is not None and (args.rule == "expected_sarsa" or args.double or args.n_step != 1 or args.evaluate):
         ap.error("--trace-decay goes with --rule q_learning or sarsa (training runs), without --double and --n-step")
+    if args.planning_steps and (args.rule != "q_learning" or args.double or args.n_step != 1 or args.trace_decay is not None
+                                or args.evaluate):
+        ap.error("--planning-steps goes with --rule q_learning (training runs), without --double, --n-step and --trace-decay")
     traces = None if args.trace_decay is None else (args.trace_decay, args.trace_length, args.trace_kind)
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
@@ -190,7 +201,12 @@ def main() -> None:
         if args.evaluate:
             pop = population_eval_rate(make_env, M, S, A, k, dtype, log, args.double)
         else:
-            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step, traces)
+            pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step, traces,
+                                  args.planning_steps)
+            if args.planning_steps:
+                pop["planning_steps"] = args.planning_steps
+                pop["event_ns_per_env_step"] = pop["kernel_ms"] * 1e6 / (pop["runs"] * pop["steps"])
+                pop["event_ns_per_table_update"] = pop["event_ns_per_env_step"] / (1 + args.planning_steps)
         base = base_cache[name]
         line = {"workload": name, "evaluate": args.evaluate, "rule": args.rule, **({"n_step": args.n_step} if args.n_step != 1 else {}), **({"trace_decay": traces[0], "trace_length": traces[1], "trace_kind": traces[2]} if traces else {}), **({"double": True} if args.double else {}), "dtype": args.dtype, "log": log, **pop, "standalone_env_steps_per_s": base["env_steps_per_s"],
                 "speedup_vs_standalone": pop["env_steps_per_s"] / base["env_steps_per_s"]}
@@ -204,6 +220,8 @@ def main() -> None:
         name = f"population_rate_{args.rule}.json" if args.n_step == 1 else f"population_rate_{args.rule}_n{args.n_step}.json"
     if traces:
         name = f"population_rate_{args.rule}_trace{args.trace_length}.json"
+    if args.planning_steps:
+        name = f"population_rate_dyna{args.planning_steps}.json"
     if args.double:
         name = name.replace(".json", "_double.json")
     (args.out / name).write_text(json.dumps(lines, indent=1))
