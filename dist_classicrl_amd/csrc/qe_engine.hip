@@ -504,15 +504,17 @@ int read_control(qe_engine* e, RolloutSlot& sl, Ctrl& fin, double& clock_ms) {
 }
 
 // Device time of a finished rollout: its event pair, else the kernel's own clock, else the last measured time per step.
-int call_time(qe_engine* e, const RolloutSlot& sl, double clock_ms, float& ms) {
+int call_time(qe_engine* e, const RolloutSlot& sl, double clock_ms, double& ms) {
     if (sl.timed) {
-        HIP_TRY(hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
-        if (sl.steps > 0) e->ms_per_step_est = (double)ms / (double)sl.steps;
+        float event_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&event_ms, sl.ev0, sl.ev1));
+        ms = (double)event_ms;
+        if (sl.steps > 0) e->ms_per_step_est = ms / (double)sl.steps;
     } else if (sl.fast) {
-        ms = (float)clock_ms;
+        ms = clock_ms;  // the in-kernel clock as it is: kernel_ms == device_clock_ms (QE_OPT_EVENT_TIMING 0)
         if (sl.steps > 0) e->ms_per_step_est = clock_ms / (double)sl.steps;
     } else {
-        ms = (float)(e->ms_per_step_est * (double)sl.steps);
+        ms = e->ms_per_step_est * (double)sl.steps;
     }
     return QE_OK;
 }
@@ -562,7 +564,7 @@ int fetch_episode_log(qe_engine* e, RolloutSlot& sl, const Ctrl& fin, long long&
     return QE_OK;
 }
 
-void fill_stats(const RolloutSlot& sl, const Ctrl& fin, float ms, double clock_ms, long long total, long long got,
+void fill_stats(const RolloutSlot& sl, const Ctrl& fin, double ms, double clock_ms, long long total, long long got,
                 qe_rollout_stats* st) {
     const bool persistent = sl.path == RolloutPath::Persistent;
     memset(st, 0, sizeof *st);
@@ -627,8 +629,7 @@ int rollout_end(qe_engine* e, RolloutSlot& sl, qe_rollout_stats* st) {
     if (!sl.busy) return qe_fail(QE_ERR_INVALID, "no rollout in flight in this slot");
     sl.busy = false;
     Ctrl fin{};
-    double clock_ms = 0.0;
-    float ms = 0;
+    double clock_ms = 0.0, ms = 0.0;
     long long total = 0, got = 0;
     if (int rc = read_control(e, sl, fin, clock_ms)) return rc;
     if (int rc = call_time(e, sl, clock_ms, ms)) return rc;

@@ -82,7 +82,8 @@ class CHashRollout:
             raise IndexError(msg)
         self.step += steps
         k = min(cnt.value, cap)
-        out = {"actions": tr, "history": er[:k].copy(), "ep_step": es[:k].copy(), "episodes": cnt.value}
+        out = {"actions": tr, "history": er[:k].copy(), "ep_step": es[:k].copy(), "ep_agent": ea[:k].copy(),
+               "episodes": cnt.value}
         if delta_log:
             self.lib.oc_set_delta_log(None, None, C.c_int64(0))
             out["cells"], out["deltas"] = d_cells, d_deltas

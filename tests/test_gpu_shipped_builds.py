@@ -35,10 +35,10 @@ def _bench_runtime(algo, sch, Runtime):
     return Runtime(algo, sch.ExponentialSchedule(0.1, 1e-5, 0.995), sch.ExponentialSchedule(1.0, 0.01, 0.995))
 
 
-def _c_oracle_run(n, S, A, steps, *, masked=False, delta_log=False):
+def _c_oracle_run(n, S, A, steps, *, masked=False, delta_log=False, dtype=np.float32, mode="iter"):
     from oracle import c_oracle
 
-    ref = c_oracle.CHashRollout(n, S, A, masked=masked, dtype=np.float32)
+    ref = c_oracle.CHashRollout(n, S, A, masked=masked, dtype=dtype, mode=mode)
     eps, _ = c_oracle.exp_schedule(1.0, 0.01, 0.995, n, steps)
     lr, _ = c_oracle.exp_schedule(0.1, 1e-5, 0.995, n, steps)
     out = ref.run(eps, lr, trace=True, delta_log=delta_log)

@@ -74,3 +74,50 @@ def test_c_oracle_follows_numpy_oracle_through_nan(spec, chunks, dt, mode, sched
         assert np.array_equal(np.concatenate(history), w["history"], equal_nan=True)
         assert np.array_equal(run.obs, w["final_obs"])
     assert any(w["raised"] for w in want) or np.isnan(want[-1]["q"]).any()
+
+
+@pytest.mark.parametrize(("n", "S", "A", "dt", "mode", "steps"), [
+    (70, 40, 4, "f4", "iter", 40),
+    (70, 40, 4, "f8", "vec", 40),
+])
+def test_c_oracle_matches_numpy_oracle_when_every_step_ends_an_episode(n, S, A, dt, mode, steps):
+    """``p_term_256=256``: every agent finishes an episode in every step, the rate at which the GPU tests fill the
+    engine's episode logs to their last entry.  The C oracle is their judge, so it is pinned here to the NumPy oracle
+    at that rate: table, actions, returns, and the log's (step, agent) keys, which must be every (t, i) exactly once,
+    t-major."""
+    from oracle.envs import HashTabularEnv
+    from oracle.qlearn_oracle import OracleQLearning, OracleRuntime, OracleSchedule
+
+    env = HashTabularEnv(n, S, A, seed=1, p_term_256=256)
+    algo = OracleQLearning(S, A, 0.99, seed=0, dtype=np.dtype(dt))
+    rt = OracleRuntime(algo, OracleSchedule("constant", 0.1, None, None), OracleSchedule("constant", 0.3, None, None),
+                       learn_mode=mode)
+    rt.trace = []
+    ends, inner = [], env.step
+
+    def step(actions):
+        out = inner(actions)
+        ends.append(np.flatnonzero(np.asarray(out[2]) | np.asarray(out[3])))
+        return out
+
+    env.step = step
+    states, _ = env.reset()
+    acc, history = np.zeros(n, dtype=np.float32), []
+    for _ in range(steps):
+        states, _ = rt.run_single_step(env, states, acc, history)
+    want_step = np.concatenate([np.full(e.size, t, dtype=np.int32) for t, e in enumerate(ends)])
+    want_agent = np.concatenate(ends).astype(np.int32)
+
+    run = c_oracle.CHashRollout(n, S, A, p_term_256=256, dtype=np.dtype(dt), mode=mode)
+    got = run.run(np.full(steps, 0.3), np.full(steps, 0.1), trace=True)
+    assert np.array_equal(got["actions"], np.stack([a for a, _, _ in rt.trace]))
+    assert np.array_equal(run.q, algo.q_table)
+    assert np.array_equal(got["history"], np.array(history, dtype=np.float32))
+    assert np.array_equal(got["ep_step"], want_step) and np.array_equal(got["ep_agent"], want_agent)
+    assert np.array_equal(run.obs, np.asarray(states, dtype=np.int32))
+    assert np.array_equal(run.acc, acc) and not acc.any()
+    assert np.array_equal(run.episode, env.episode)
+    # the log is exactly (t, i) for every t, then every i
+    assert got["episodes"] == steps * n
+    assert np.array_equal(got["ep_step"], np.repeat(np.arange(steps, dtype=np.int32), n))
+    assert np.array_equal(got["ep_agent"], np.tile(np.arange(n, dtype=np.int32), steps))
