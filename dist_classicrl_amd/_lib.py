@@ -238,6 +238,8 @@ PROTOTYPES = {
     "qe_population_planning": (C.c_int, [_P]),
     "qe_population_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
     "qe_population_set_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
+    "qe_env_table_solve": (C.c_int, [_P, C.c_double, C.c_double, C.c_int32, _F64P, _F64P, _I32P, _F64P]),
+    "qe_population_policy_values": (C.c_int, [_P, _P, _F64P, C.c_double, C.c_int32, _F64P, _I32P, _F64P, _U32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "qe_debug_set_turn_epoch": (C.c_int, [_P, C.c_uint64]),
     "qe_debug_turn_epoch": (C.c_uint64, [_P]),

@@ -67,7 +67,7 @@ from typing import NamedTuple
 import numpy as np
 
 from dist_classicrl_amd import _lib
-from dist_classicrl_amd.environments.device_envs import DeviceVecEnv
+from dist_classicrl_amd.environments.device_envs import DeviceVecEnv, check_discounts, check_solve_args, start_value
 from dist_classicrl_amd.schedules import BaseSchedule, ConstantSchedule, ExponentialSchedule, LinearSchedule
 
 SCHED_CONSTANT, SCHED_LINEAR, SCHED_EXPONENTIAL = 0, 1, 2
@@ -150,6 +150,17 @@ class PopulationTraining(NamedTuple):
 
     def run_reward_history(self, r: int) -> np.ndarray:
         return self.returns[self.offsets[r]:self.offsets[r + 1]]
+
+
+class PolicyValues(NamedTuple):
+    """:meth:`QLearningPopulation.policy_values`: the exact value of every run's greedy policy on a table MDP."""
+
+    values: np.ndarray        # float64[M, S]  V of run r's greedy policy (NaN for a run with status bit 1)
+    start_values: np.ndarray  # float64[M]     sum over the start support of p_i * values[r, start_state_i]
+    sweeps: np.ndarray        # int32[M]       the sweep each run froze at (or max_sweeps; 0 with status bit 1)
+    residuals: np.ndarray     # float64[M]     max_s |V_t - V_{t-1}| of that sweep
+    converged: np.ndarray     # bool[M]        residual <= tol
+    status: np.ndarray        # uint32[M]      bit 0: a state without a valid action; bit 1: a NaN in a valid cell
 
 
 def pending_array(values, runs) -> np.ndarray | None:
@@ -759,6 +770,35 @@ class QLearningPopulation:
             msg = f"the environment has {env.num_agents} agents, the population {self.runs} runs: one agent per run"
             raise ValueError(msg)
 
+    def policy_values(self, env, discount_factor=None, tol=1e-12, max_sweeps=100_000) -> PolicyValues:
+        """The exact value of every run's greedy policy on ``env``, a :class:`TabularMDPEnv` of ``num_agents == runs``,
+        by iterative policy evaluation on the device (``qe_population_policy_values``): no sampling, no draw.  The policy
+        is the one :meth:`evaluate_episodes` follows -- the maximum of the valid columns of the run's row (``double_q``:
+        of A + B), ties broken uniformly -- and the law the integer one the environment samples from.  ``discount_factor``
+        is a number, a sequence of ``runs``, or None for the runs' own; 1.0 gives the undiscounted return
+        :meth:`evaluate_episodes` reports.  Each run stops at its first sweep with residual ``<= tol``, else at
+        ``max_sweeps``.  Tables, schedules, draw counters and the environment's state are left as they are."""
+        self._check_env(env)
+        gammas = None
+        if discount_factor is not None:
+            gammas = np.ascontiguousarray(np.broadcast_to(check_discounts(
+                _per_run(discount_factor, self.runs, "discount_factor")), (self.runs,)))
+        tol, max_sweeps = check_solve_args(tol, max_sweeps)
+        env.bind(self)  # (an environment that is not a table MDP is the library's to refuse: NotImplementedError)
+        M, S = self.runs, self.state_size
+        values = np.empty((M, S), dtype=np.float64)
+        sweeps = np.empty(M, dtype=np.int32)
+        residuals = np.empty(M, dtype=np.float64)
+        status = np.empty(M, dtype=np.uint32)
+        rc = self._lib.qe_population_policy_values(self._h, env.handle, _lib.ptr(gammas, C.c_double), tol, max_sweeps,
+                                                   _lib.ptr(values, C.c_double), _lib.ptr(sweeps, C.c_int32),
+                                                   _lib.ptr(residuals, C.c_double), _lib.ptr(status, C.c_uint32))
+        _lib.check(rc)
+        starts = np.array([start_value(env.mdp, values[r]) for r in range(M)], dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            converged = residuals <= tol
+        return PolicyValues(values, starts, sweeps, residuals, converged, status)
+
     def evaluate_steps(self, env, steps, log=True) -> PopulationEval:
         """Greedy evaluation: every run takes ``steps`` steps from ``env.reset(seed=42)`` with its own table, as the
         standalone one-agent ``evaluate_steps(env_r, steps)``.  Tables and schedules are untouched; every run's draw
@@ -868,5 +908,5 @@ class QLearningPopulation:
                                   np.array(val_finished, dtype=bool).reshape(shape), segments, state_dict)
 
 
-__all__ = ["PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
+__all__ = ["PolicyValues", "PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
            "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "window_arrays"]

@@ -5,6 +5,7 @@ from .device_envs import (
     DeviceVecEnv,
     GridLakeEnv,
     HashTabularEnv,
+    MDPSolution,
     RiggedTwoArmedBanditVecEnv,
     TableMDP,
     TabularMDPEnv,
@@ -12,5 +13,5 @@ from .device_envs import (
     encode_table_mdp,
 )
 
-__all__ = ["DeviceVecEnv", "GridLakeEnv", "HashTabularEnv", "RiggedTwoArmedBanditVecEnv", "TableMDP", "TabularMDPEnv",
+__all__ = ["DeviceVecEnv", "GridLakeEnv", "HashTabularEnv", "MDPSolution", "RiggedTwoArmedBanditVecEnv", "TableMDP", "TabularMDPEnv",
            "TicTacToeEnv", "encode_table_mdp"]

@@ -261,6 +261,79 @@ class TableMDP(NamedTuple):
     def k(self) -> int:
         return int(self.thr.shape[2])
 
+    def outcome_weights(self) -> np.ndarray:
+        """``uint64[S, A, K]``: the integer weight of every slot under the sampling rule, out of ``2**32`` -- the number
+        of 32-bit words ``u`` for which the rule "first ``j < K - 1`` with ``u < thr[j]``, else slot ``K - 1``" takes
+        slot ``j`` (the device records carry ``2**32 - 1`` in slot ``K - 1``, which the rule never reads).  With a
+        running maximum ``t = 0``: ``w_j = max(0, thr_j - t)`` then ``t = max(t, thr_j)`` for ``j < K - 1``, and
+        ``w_{K-1} = 2**32 - t``.  ``w * 2.0**-32`` is the slot's exact probability; padding copies of the last outcome
+        share its mass with it."""
+        return _slot_weights(self.thr)
+
+    def start_weights(self) -> np.ndarray:
+        """``uint64[n_start]``: the weights of the start support, by the rule of :meth:`outcome_weights`."""
+        return _slot_weights(self.start_thr)
+
+
+def _slot_weights(thr: np.ndarray) -> np.ndarray:
+    """Weights out of 2**32 of "the first j below the last with u < thr[j], else the last" along the last axis."""
+    t = np.asarray(thr, dtype=np.uint64)
+    w = np.empty(t.shape, dtype=np.uint64)
+    top = np.zeros(t.shape[:-1], dtype=np.uint64)
+    for j in range(t.shape[-1] - 1):
+        w[..., j] = np.where(t[..., j] > top, t[..., j] - top, np.uint64(0))
+        top = np.maximum(top, t[..., j])
+    w[..., -1] = np.uint64(1 << 32) - top
+    return w
+
+
+class MDPSolution(NamedTuple):
+    """:meth:`TabularMDPEnv.solve`: value iteration's result for the MDP the environment samples from."""
+
+    q: np.ndarray        # float64[S, A]  Q_t of the last sweep t (masked cells included)
+    v: np.ndarray        # float64[S]     V_t: the maximum of the valid columns, 0.0 for a state without one
+    start_value: float   # sum over the start support of p_i * V[start_state_i]
+    sweeps: int          # t
+    residual: float      # max_s |V_t[s] - V_{t-1}[s]|
+    converged: bool      # residual <= tol (else stopped by max_sweeps)
+
+
+def start_value(mdp: "TableMDP", v: np.ndarray) -> float:
+    """``sum_i p_i * v[start_state_i]`` over the start support, ascending, accumulated sequentially in float64."""
+    acc = 0.0
+    for w, s in zip(mdp.start_weights().tolist(), mdp.start_state.tolist()):
+        if w:
+            acc = acc + (float(w) * 2.0 ** -32) * float(v[s])
+    return acc
+
+
+def check_solve_args(tol, max_sweeps) -> tuple[float, int]:
+    """``(tol, max_sweeps)`` of a dynamic-programming call, or ``ValueError``."""
+    try:
+        tol_f = float(tol)
+    except (TypeError, ValueError):
+        tol_f = float("nan")
+    if not (tol_f >= 0.0 and np.isfinite(tol_f)):
+        msg = f"tol must be a finite number >= 0, got {tol!r}"
+        raise ValueError(msg)
+    if (isinstance(max_sweeps, (bool, np.bool_)) or not isinstance(max_sweeps, (int, np.integer))
+            or not 1 <= max_sweeps < 2 ** 31):
+        msg = f"max_sweeps must be an integer in 1 .. 2^31 - 1, got {max_sweeps!r}"
+        raise ValueError(msg)
+    return tol_f, int(max_sweeps)
+
+
+def check_discounts(discount_factor, what="discount_factor") -> np.ndarray:
+    """Discounts as a float64 array, each a finite number in [0, 1], or ``ValueError``."""
+    try:
+        g = np.asarray(discount_factor, dtype=np.float64)
+    except (TypeError, ValueError):
+        g = np.array(np.nan)
+    if g.size == 0 or not ((g >= 0.0) & (g <= 1.0)).all():
+        msg = f"{what}: every discount must be a finite number in [0, 1], got {discount_factor!r}"
+        raise ValueError(msg)
+    return g
+
 
 def _thresholds(p: np.ndarray) -> np.ndarray:
     """uint32 thresholds of probability lists along the last axis (zero-probability entries compacted away)."""
@@ -452,6 +525,27 @@ class TabularMDPEnv(DeviceVecEnv):
         mdp = encode_table_mdp(np.ones(nxt.shape + (1,)), nxt[..., None], rew[..., None], term[..., None],
                                initial_state_distrib, action_masks)
         return cls(num_agents, mdp, seed=seed, agent_offset=agent_offset)
+
+    def solve(self, discount_factor, tol=1e-12, max_sweeps=100_000) -> MDPSolution:
+        """Q*, V* of the MDP by value iteration on the device (``qe_env_table_solve``; needs a bound environment).
+        ``V_0 = 0``; sweep ``t`` backs every cell up over ``V_{t-1}`` and stops at the first ``t`` whose residual
+        ``max_s |V_t[s] - V_{t-1}[s]|`` is ``<= tol``, else at ``max_sweeps``.  The law is the integer one the
+        environment samples from (:meth:`TableMDP.outcome_weights`), all arithmetic float64: the result is defined to
+        the bit.  Nothing of the environment's or the algorithm's state is touched."""
+        gamma = check_discounts(discount_factor)
+        if gamma.ndim != 0:
+            msg = f"discount_factor must be one number, got {discount_factor!r}"
+            raise ValueError(msg)
+        tol, max_sweeps = check_solve_args(tol, max_sweeps)
+        self._need()
+        q = np.empty((self.state_size, self.action_size), dtype=np.float64)
+        v = np.empty(self.state_size, dtype=np.float64)
+        sweeps = C.c_int32()
+        residual = C.c_double()
+        rc = self._lib.qe_env_table_solve(self._h, float(gamma), tol, max_sweeps, _lib.ptr(q, C.c_double),
+                                          _lib.ptr(v, C.c_double), C.byref(sweeps), C.byref(residual))
+        _lib.check(rc)
+        return MDPSolution(q, v, start_value(self.mdp, v), int(sweeps.value), float(residual.value), rc == 1)
 
     def _create(self, algorithm) -> None:
         m = self.mdp

@@ -471,6 +471,43 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
 int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
                             const int32_t* visited, const int32_t* count);
 
+/* ---- dynamic programming over a QE_ENV_TABLE environment (Sutton & Barto ch. 4; csrc/qe_mdp_solve.h) ------------------
+ * The MDP is the law the environment samples from, read from its device records.  For (s, a) with k slots and a running
+ * maximum t = 0: slot j < k - 1 weighs w_j = max(0, thr_j - t), then t = max(t, thr_j); slot k - 1 weighs 2^32 - t;
+ * p_j = w_j * 2^-32 (exact in float64).  Backup of a cell over a float64 value vector V:
+ *     acc = 0.0;  for j ascending with w_j > 0:  x = double(r_j) + (terminated_j ? 0.0 : gamma * V[next_j]);  acc = acc + p_j * x
+ * (one product, one add, no contraction; a terminated outcome bootstraps 0 and the auto-reset successor plays no part).
+ * The valid columns of s are the environment's mask for s, or all of them; a state without one has value 0.0.
+ *
+ * qe_env_table_solve: value iteration.  V_0 = 0; sweep t >= 1: Q_t[s,a] = backup(s, a; V_{t-1}) for every cell, masked ones
+ * included, V_t[s] = max over the valid a, res_t = max_s |V_t[s] - V_{t-1}[s]|; every sweep reads only V_{t-1}.  The result
+ * is (Q_t, V_t) of the first t with res_t <= tol, else of t = max_sweeps; *sweeps_out = t, *residual_out = res_t.  Returns
+ * 1 = stopped by tol, 0 = by max_sweeps.  gamma in [0, 1], tol >= 0, both finite, 1 <= max_sweeps: else QE_ERR_INVALID.  An
+ * environment of another kind is QE_ERR_UNSUPPORTED.  Any action_size a device environment admits; works on the
+ * environment of a population engine as well (the MDP of one run).
+ *
+ * qe_population_policy_values: the exact value of every run's greedy policy.  In state s of run r, row = the run's table
+ * row in the table dtype (double estimator on: A[s,.] + B[s,.], one addition in that dtype, as its greedy evaluation forms
+ * it), m = the maximum of the valid columns, G = the valid columns with row[a] == m: greedy selection with uniform
+ * tie-breaking, as qe_population_evaluate performs it (the 2^-32 bias of its pick is ignored).  V_0[r,.] = 0;
+ *     V_t[r,s] = (sum over a in G, ascending, from 0.0, of backup(s, a; V_{t-1}[r,.])) / double(|G|),  0.0 if G is empty;
+ * res_t[r] = max_s |V_t[r,s] - V_{t-1}[r,s]|.  Run r freezes at its first t with res_t[r] <= tol: v_out[r,.] = V_t[r,.],
+ * sweeps_out[r] = t, residual_out[r] = res_t[r], and later sweeps neither read nor write it; else it stops at max_sweeps.
+ * gammas: one discount per run, each in [0, 1], or NULL for the runs' own (qe_population_configure); 1.0 gives the
+ * undiscounted return qe_population_evaluate reports.  status_out[r]: bit 0 = some state of the run has no valid column
+ * (informational), bit 1 = a valid cell of the run's row (as formed above) is NaN: its values and residual are NaN and its
+ * sweeps 0.  Returns the number of runs stopped by tol.  Tables, schedules, draw counters, environment state, windows,
+ * traces and model are not touched; any output may be NULL.  An engine that is not a population, or not the
+ * environment's, is QE_ERR_INVALID.
+ *
+ * Both enqueue their sweeps in batches on the engine's stream and synchronise once per batch; their device buffers live
+ * for the call (allocation failure: QE_ERR_OOM, nothing stays allocated). */
+int qe_env_table_solve(qe_env* env, double gamma, double tol, int32_t max_sweeps, double* q_out /* S*A or NULL */,
+                       double* v_out /* S or NULL */, int32_t* sweeps_out, double* residual_out);
+int qe_population_policy_values(qe_engine* e, qe_env* env, const double* gammas /* runs; NULL = the runs' own */, double tol,
+                                int32_t max_sweeps, double* v_out /* runs*S */, int32_t* sweeps_out, double* residual_out,
+                                uint32_t* status_out /* each runs, may be NULL */);
+
 /* ---- diagnostics -----------------------------------------------------------------------------------
  * Occupies `blocks` CUs (one workgroup each, most of a CU's LDS) for `microseconds` (at most 200 000) on a stream of its
  * own and returns at once: tests take part of the chip away with it while a rollout runs, the situation of a collective
