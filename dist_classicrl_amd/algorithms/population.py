@@ -175,73 +175,86 @@ def pending_array(values, runs) -> np.ndarray | None:
     return np.ascontiguousarray(arr, dtype=np.int32)
 
 
+# Dict-valued per-run state as the library takes it: one (key, shape, accepted dtype kinds, target dtype) per array, in
+# the order of the library's arguments.
+_CTYPES = {np.dtype(np.int32): C.c_int32, np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double,
+           np.dtype(np.uint8): C.c_uint8}
+
+
+def _window_specs(runs, n_step):
+    slots = (runs, n_step - 1)
+    return (("length", (runs,), "iu", np.int32), ("states", slots, "iu", np.int32), ("actions", slots, "iu", np.int32),
+            ("rewards", slots, "fiu", np.float32))
+
+
+def _trace_specs(runs, trace_length):
+    slots = (runs, trace_length)
+    return ("states", slots, "iu", np.int32), ("actions", slots, "iu", np.int32), ("values", slots, "fiu", np.float64)
+
+
+def _model_specs(runs, state_size, action_size):
+    cells = (runs, state_size, action_size)
+    return (("next_states", cells, "iu", np.int32), ("rewards", cells, "f", np.float32), ("terminated", cells, "b", np.uint8),
+            ("visited", (runs, state_size * action_size), "iu", np.int32), ("count", (runs,), "iu", np.int32))
+
+
+def _spec_arrays(what, value, specs, exact=False) -> tuple | None:
+    """The dict ``value`` (``what`` names it) as the tuple of contiguous arrays ``specs`` describes; None for None and
+    ``ValueError`` on anything else.  ``exact``: no cast may change a value -- a float must be exact in the target dtype
+    and an integer lie inside int32."""
+    if value is None:
+        return None
+    names = [repr(key) for key, *_ in specs]
+    if not isinstance(value, dict) or sorted(value) != sorted(key for key, *_ in specs):
+        msg = f"{what}: expected a dict with the keys {', '.join(names[:-1])} and {names[-1]}"
+        raise ValueError(msg)
+    out = []
+    for key, shape, kinds, dtype in specs:
+        arr = np.asarray(value[key])
+        lossy = (exact and kinds == "f" and arr.dtype.kind == "f" and arr.dtype.itemsize > np.dtype(dtype).itemsize
+                 and not np.array_equal(arr.astype(dtype), arr, equal_nan=True))
+        if arr.shape != shape or arr.dtype.kind not in kinds or lossy:
+            want = "bool" if kinds == "b" else np.dtype(dtype)
+            msg = f"{what}[{key!r}]: expected shape {shape} of {want}, got shape {arr.shape} of {arr.dtype}"
+            raise ValueError(msg)
+        if exact and kinds == "iu" and arr.size and (arr.min() < -(2 ** 31) or arr.max() >= 2 ** 31):
+            msg = f"{what}[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got values outside int32"
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(arr, dtype=dtype))
+    return tuple(out)
+
+
 def window_arrays(window, runs, n_step) -> tuple | None:
     """``n_step_window`` of a state dict as the ``(length, states, actions, rewards)`` arrays the library takes (None:
     every window empty): int32 ``[runs]``, int32 ``[runs, n_step - 1]`` twice and float32 ``[runs, n_step - 1]``;
     ``ValueError`` on anything else."""
-    if window is None:
-        return None
-    if not isinstance(window, dict) or sorted(window) != ["actions", "length", "rewards", "states"]:
-        msg = "n_step_window: expected a dict with the keys 'length', 'states', 'actions' and 'rewards'"
-        raise ValueError(msg)
-    out = []
-    for key, shape, kinds, dtype in (("length", (runs,), "iu", np.int32), ("states", (runs, n_step - 1), "iu", np.int32),
-                                     ("actions", (runs, n_step - 1), "iu", np.int32),
-                                     ("rewards", (runs, n_step - 1), "fiu", np.float32)):
-        arr = np.asarray(window[key])
-        if arr.shape != shape or arr.dtype.kind not in kinds:
-            msg = f"n_step_window[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got shape {arr.shape} of {arr.dtype}"
-            raise ValueError(msg)
-        out.append(np.ascontiguousarray(arr, dtype=dtype))
-    return tuple(out)
+    return _spec_arrays("n_step_window", window, _window_specs(runs, n_step))
 
 
 def trace_arrays(traces, runs, trace_length) -> tuple | None:
     """``eligibility_traces`` of a state dict as the ``(states, actions, values)`` arrays the library takes (None: every
     slot free): int32 ``[runs, trace_length]`` twice and float64 ``[runs, trace_length]``; ``ValueError`` on anything
     else."""
-    if traces is None:
-        return None
-    if not isinstance(traces, dict) or sorted(traces) != ["actions", "states", "values"]:
-        msg = "eligibility_traces: expected a dict with the keys 'states', 'actions' and 'values'"
-        raise ValueError(msg)
-    out = []
-    shape = (runs, trace_length)
-    for key, kinds, dtype in (("states", "iu", np.int32), ("actions", "iu", np.int32), ("values", "fiu", np.float64)):
-        arr = np.asarray(traces[key])
-        if arr.shape != shape or arr.dtype.kind not in kinds:
-            msg = f"eligibility_traces[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got shape {arr.shape} of {arr.dtype}"
-            raise ValueError(msg)
-        out.append(np.ascontiguousarray(arr, dtype=dtype))
-    return tuple(out)
+    return _spec_arrays("eligibility_traces", traces, _trace_specs(runs, trace_length))
 
 
 def model_arrays(model, runs, state_size, action_size) -> tuple | None:
     """A ``planning_model`` as the ``(next_states, rewards, terminated, visited, count)`` arrays the library takes (None:
     nothing is known): int32 ``[runs, S, A]``, float32 ``[runs, S, A]``, uint8 ``[runs, S, A]``, int32 ``[runs, S * A]`` and
     int32 ``[runs]``; ``ValueError`` on anything else.  Whether list and model agree is the library's check."""
-    if model is None:
-        return None
-    keys = ["count", "next_states", "rewards", "terminated", "visited"]
-    if not isinstance(model, dict) or sorted(model) != keys:
-        msg = "planning_model: expected a dict with the keys 'next_states', 'rewards', 'terminated', 'visited' and 'count'"
+    return _spec_arrays("planning_model", model, _model_specs(runs, state_size, action_size), exact=True)
+
+
+# The per-run state a training call hands to the next one through the state dict: the dict's key, which is also the
+# population's property, and whether a population carries it.  (The planning model is knowledge, not such state.)
+_CARRIED = {"pending_actions": lambda pop: pop.update_rule == "sarsa", "n_step_window": lambda pop: pop.n_step > 1,
+            "eligibility_traces": lambda pop: pop.trace_decay is not None}
+
+
+def _check_int(name, value, lo, hi) -> None:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+        msg = f"{name} must be an integer in {lo} .. {hi}, got {value!r}"
         raise ValueError(msg)
-    cells = (runs, state_size, action_size)
-    out = []
-    for key, shape, kinds, dtype in (("next_states", cells, "iu", np.int32), ("rewards", cells, "f", np.float32),
-                                     ("terminated", cells, "b", np.uint8), ("visited", (runs, state_size * action_size), "iu", np.int32),
-                                     ("count", (runs,), "iu", np.int32)):
-        arr = np.asarray(model[key])
-        if arr.shape != shape or arr.dtype.kind not in kinds or (key == "rewards" and arr.dtype.itemsize > 4
-                                                                 and not np.array_equal(arr.astype(np.float32), arr, equal_nan=True)):
-            want = "bool" if key == "terminated" else np.dtype(dtype)
-            msg = f"planning_model[{key!r}]: expected shape {shape} of {want}, got shape {arr.shape} of {arr.dtype}"
-            raise ValueError(msg)
-        if kinds == "iu" and arr.size and (arr.min() < -(2 ** 31) or arr.max() >= 2 ** 31):
-            msg = f"planning_model[{key!r}]: expected shape {shape} of {np.dtype(dtype)}, got values outside int32"
-            raise ValueError(msg)
-        out.append(np.ascontiguousarray(arr, dtype=dtype))
-    return tuple(out)
 
 
 def _per_run(value, runs, what):
@@ -288,9 +301,7 @@ class QLearningPopulation:
         if double_q and update_rule != "q_learning":
             msg = f"double_q=True is Double Q-learning: it needs update_rule='q_learning', got {update_rule!r}"
             raise ValueError(msg)
-        if isinstance(n_step, (bool, np.bool_)) or not isinstance(n_step, (int, np.integer)) or not 1 <= n_step <= _lib.N_STEP_MAX:
-            msg = f"n_step must be an integer in 1 .. {_lib.N_STEP_MAX}, got {n_step!r}"
-            raise ValueError(msg)
+        _check_int("n_step", n_step, 1, _lib.N_STEP_MAX)
         if n_step > 1 and double_q:
             msg = f"n_step={n_step} with double_q=True: the double estimator is a one-step method"
             raise ValueError(msg)
@@ -298,10 +309,7 @@ class QLearningPopulation:
             msg = (f"n_step={n_step} needs update_rule='sarsa' or 'expected_sarsa': an uncorrected n-step Q-learning is not an "
                    "off-policy method (importance sampling and tree backup are not built)")
             raise ValueError(msg)
-        if (isinstance(planning_steps, (bool, np.bool_)) or not isinstance(planning_steps, (int, np.integer))
-                or not 0 <= planning_steps <= _lib.PLANNING_MAX):
-            msg = f"planning_steps must be an integer in 0 .. {_lib.PLANNING_MAX}, got {planning_steps!r}"
-            raise ValueError(msg)
+        _check_int("planning_steps", planning_steps, 0, _lib.PLANNING_MAX)
         if planning_steps > 0:
             if update_rule != "q_learning":
                 msg = (f"planning_steps={planning_steps} needs update_rule='q_learning', got {update_rule!r}: Dyna-Q replays "
@@ -340,10 +348,7 @@ class QLearningPopulation:
             if n_step > 1:
                 msg = f"trace_decay with n_step={n_step}: one multi-step method at a time"
                 raise ValueError(msg)
-            if (isinstance(trace_length, (bool, np.bool_)) or not isinstance(trace_length, (int, np.integer))
-                    or not 1 <= trace_length <= _lib.TRACE_MAX):
-                msg = f"trace_length must be an integer in 1 .. {_lib.TRACE_MAX}, got {trace_length!r}"
-                raise ValueError(msg)
+            _check_int("trace_length", trace_length, 1, _lib.TRACE_MAX)
             if trace_kind not in _lib.TRACE_KINDS:
                 msg = f"trace_kind must be one of {', '.join(map(repr, _lib.TRACE_KINDS))}, got {trace_kind!r}"
                 raise ValueError(msg)
@@ -376,8 +381,9 @@ class QLearningPopulation:
         self.last_stats = None
         self._lib = _lib.load()
         self._h = C.c_void_p()
+        self._dtype_code = _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64
         _lib.check(self._lib.qe_create_population(C.byref(self._h), self.runs, self.state_size, self.action_size, self.seed,
-                                                  _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64, int(device)))
+                                                  self._dtype_code, int(device)))
         _lib.check(self._lib.qe_population_configure(self._h, None, None, _lib.ptr(self.discount_factor, C.c_double)))
         if update_rule != "q_learning":
             _lib.check(self._lib.qe_population_set_update_rule(self._h, _lib.UPDATE_RULES[update_rule]))
@@ -447,6 +453,16 @@ class QLearningPopulation:
     def pending_actions(self, values) -> None:
         _lib.check(self._lib.qe_population_set_pending_actions(self._h, _lib.ptr(pending_array(values, self.runs), C.c_int32)))
 
+    def _state_dict_of(self, getter, specs) -> dict:
+        """Fresh arrays as ``specs`` describes them, filled by the library's ``getter``."""
+        out = {key: np.empty(shape, dtype=dtype) for key, shape, _, dtype in specs}
+        _lib.check(getter(self._h, *(_lib.ptr(arr, _CTYPES[arr.dtype]) for arr in out.values())))
+        return out
+
+    def _set_state(self, setter, arrays, count) -> None:
+        """What a ``*_arrays`` function returned (None: ``count`` NULLs, the empty state) through the library's ``setter``."""
+        _lib.check(setter(self._h, *([None] * count if arrays is None else [_lib.ptr(arr, _CTYPES[arr.dtype]) for arr in arrays])))
+
     @property
     def n_step_window(self) -> dict | None:
         """``n_step > 1``: every run's window of transitions not yet updated, a dict of ``length`` (int32 ``[runs]``),
@@ -454,13 +470,7 @@ class QLearningPopulation:
         oldest first and unused slots hold 0.  ``n_step == 1``: None.  Setting None empties every window."""
         if self.n_step == 1:
             return None
-        shape = (self.runs, self.n_step - 1)
-        length = np.empty(self.runs, dtype=np.int32)
-        states, actions = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
-        rewards = np.empty(shape, dtype=np.float32)
-        _lib.check(self._lib.qe_population_window(self._h, _lib.ptr(length, C.c_int32), _lib.ptr(states, C.c_int32),
-                                                  _lib.ptr(actions, C.c_int32), _lib.ptr(rewards, C.c_float)))
-        return {"length": length, "states": states, "actions": actions, "rewards": rewards}
+        return self._state_dict_of(self._lib.qe_population_window, _window_specs(self.runs, self.n_step))
 
     @n_step_window.setter
     def n_step_window(self, window) -> None:
@@ -469,13 +479,7 @@ class QLearningPopulation:
                 msg = "a population with n_step=1 has no window"
                 raise ValueError(msg)
             return
-        arrays = window_arrays(window, self.runs, self.n_step)
-        if arrays is None:
-            _lib.check(self._lib.qe_population_set_window(self._h, None, None, None, None))
-            return
-        length, states, actions, rewards = arrays
-        _lib.check(self._lib.qe_population_set_window(self._h, _lib.ptr(length, C.c_int32), _lib.ptr(states, C.c_int32),
-                                                      _lib.ptr(actions, C.c_int32), _lib.ptr(rewards, C.c_float)))
+        self._set_state(self._lib.qe_population_set_window, window_arrays(window, self.runs, self.n_step), 4)
 
     @property
     def eligibility_traces(self) -> dict | None:
@@ -484,12 +488,7 @@ class QLearningPopulation:
         ``(0, 0, 0.0)``.  Without traces: None.  Setting None frees every slot."""
         if self.trace_decay is None:
             return None
-        shape = (self.runs, self.trace_length)
-        states, actions = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.int32)
-        values = np.empty(shape, dtype=np.float64)
-        _lib.check(self._lib.qe_population_traces(self._h, _lib.ptr(states, C.c_int32), _lib.ptr(actions, C.c_int32),
-                                                  _lib.ptr(values, C.c_double)))
-        return {"states": states, "actions": actions, "values": values}
+        return self._state_dict_of(self._lib.qe_population_traces, _trace_specs(self.runs, self.trace_length))
 
     @eligibility_traces.setter
     def eligibility_traces(self, traces) -> None:
@@ -498,13 +497,7 @@ class QLearningPopulation:
                 msg = "a population without trace_decay has no eligibility traces"
                 raise ValueError(msg)
             return
-        arrays = trace_arrays(traces, self.runs, self.trace_length)
-        if arrays is None:
-            _lib.check(self._lib.qe_population_set_trace_state(self._h, None, None, None))
-            return
-        states, actions, values = arrays
-        _lib.check(self._lib.qe_population_set_trace_state(self._h, _lib.ptr(states, C.c_int32), _lib.ptr(actions, C.c_int32),
-                                                           _lib.ptr(values, C.c_double)))
+        self._set_state(self._lib.qe_population_set_trace_state, trace_arrays(traces, self.runs, self.trace_length), 3)
 
     @property
     def planning_model(self) -> dict | None:
@@ -516,13 +509,9 @@ class QLearningPopulation:
         number of seen cells, is a ``ValueError``."""
         if not self.planning_steps:
             return None
-        cells = (self.runs, self.state_size, self.action_size)
-        nxt, rew, term = np.empty(cells, dtype=np.int32), np.empty(cells, dtype=np.float32), np.empty(cells, dtype=np.uint8)
-        visited = np.empty((self.runs, self.state_size * self.action_size), dtype=np.int32)
-        count = np.empty(self.runs, dtype=np.int32)
-        _lib.check(self._lib.qe_population_model(self._h, _lib.ptr(nxt, C.c_int32), _lib.ptr(rew, C.c_float), _lib.ptr(term, C.c_uint8),
-                                                 _lib.ptr(visited, C.c_int32), _lib.ptr(count, C.c_int32)))
-        return {"next_states": nxt, "rewards": rew, "terminated": term.astype(bool), "visited": visited, "count": count}
+        model = self._state_dict_of(self._lib.qe_population_model, _model_specs(self.runs, self.state_size, self.action_size))
+        model["terminated"] = model["terminated"].astype(bool)
+        return model
 
     @planning_model.setter
     def planning_model(self, model) -> None:
@@ -531,14 +520,7 @@ class QLearningPopulation:
                 msg = "a population without planning_steps has no planning model"
                 raise ValueError(msg)
             return
-        arrays = model_arrays(model, self.runs, self.state_size, self.action_size)
-        if arrays is None:
-            _lib.check(self._lib.qe_population_set_model(self._h, None, None, None, None, None))
-            return
-        nxt, rew, term, visited, count = arrays
-        _lib.check(self._lib.qe_population_set_model(self._h, _lib.ptr(nxt, C.c_int32), _lib.ptr(rew, C.c_float),
-                                                     _lib.ptr(term, C.c_uint8), _lib.ptr(visited, C.c_int32),
-                                                     _lib.ptr(count, C.c_int32)))
+        self._set_state(self._lib.qe_population_set_model, model_arrays(model, self.runs, self.state_size, self.action_size), 5)
 
     def save_model(self, filename) -> None:
         """:attr:`planning_model` as one ``.npz`` (``ValueError`` without planning)."""
@@ -560,47 +542,46 @@ class QLearningPopulation:
         return int(counters[0]) if (counters == counters[0]).all() else counters.view(np.int64)
 
     # ------------------------------------------------------------------ tables
-    @property
-    def q_tables(self) -> np.ndarray:
-        """All tables, ``(runs, state_size, action_size)`` (``double_q``: the tables A)."""
-        host = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
-        _lib.check(self._lib.qe_table_download(self._h, host.ctypes.data, _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64))
-        return host
-
     def _need_double(self) -> None:
         if not self.double_q:
             msg = "a population without double_q has no second table"
             raise ValueError(msg)
 
+    def _download(self, second, r=None) -> np.ndarray:
+        """All tables A (``second``: B, which needs ``double_q``), or with ``r`` run ``r``'s."""
+        if second:
+            self._need_double()
+        if r is None:
+            host = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
+            download = self._lib.qe_population_table_b_download if second else self._lib.qe_table_download
+            _lib.check(download(self._h, host.ctypes.data, self._dtype_code))
+            return host
+        r = int(r)
+        if not 0 <= r < self.runs:
+            msg = f"run {r} out of range [0, {self.runs})"
+            raise IndexError(msg)
+        host = np.empty((self.state_size, self.action_size), dtype=self.dtype)
+        download = self._lib.qe_population_table_b_download_rows if second else self._lib.qe_table_download_rows
+        _lib.check(download(self._h, host.ctypes.data, r * self.state_size, self.state_size))
+        return host
+
+    @property
+    def q_tables(self) -> np.ndarray:
+        """All tables, ``(runs, state_size, action_size)`` (``double_q``: the tables A)."""
+        return self._download(False)
+
     @property
     def q_tables_b(self) -> np.ndarray:
         """``double_q``: all tables B, ``(runs, state_size, action_size)``."""
-        self._need_double()
-        host = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
-        _lib.check(self._lib.qe_population_table_b_download(self._h, host.ctypes.data,
-                                                            _lib.QE_F32 if self.dtype == np.float32 else _lib.QE_F64))
-        return host
+        return self._download(True)
 
     def q_table_b(self, r: int) -> np.ndarray:
         """``double_q``: run ``r``'s table B, ``(state_size, action_size)``."""
-        self._need_double()
-        r = int(r)
-        if not 0 <= r < self.runs:
-            msg = f"run {r} out of range [0, {self.runs})"
-            raise IndexError(msg)
-        host = np.empty((self.state_size, self.action_size), dtype=self.dtype)
-        _lib.check(self._lib.qe_population_table_b_download_rows(self._h, host.ctypes.data, r * self.state_size, self.state_size))
-        return host
+        return self._download(True, r)
 
     def q_table(self, r: int) -> np.ndarray:
         """Run ``r``'s table, ``(state_size, action_size)``."""
-        r = int(r)
-        if not 0 <= r < self.runs:
-            msg = f"run {r} out of range [0, {self.runs})"
-            raise IndexError(msg)
-        host = np.empty((self.state_size, self.action_size), dtype=self.dtype)
-        _lib.check(self._lib.qe_table_download_rows(self._h, host.ctypes.data, r * self.state_size, self.state_size))
-        return host
+        return self._download(False, r)
 
     def _upload_form(self, tables):
         arr = np.asarray(tables)
@@ -658,11 +639,46 @@ class QLearningPopulation:
         eps = np.empty(self.runs, dtype=np.float64)
         lr = np.empty(self.runs, dtype=np.float64)
         _lib.check(self._lib.qe_population_schedules(self._h, _lib.ptr(eps, C.c_double), _lib.ptr(lr, C.c_double)))
-        for schedules, values in ((self.exploration_rate_schedules, eps), (self.lr_schedules, lr)):
-            last = {id(s): (s, r) for r, s in enumerate(schedules)}  # (a shared schedule: its runs hold the same value)
-            for s, r in last.values():
-                s.set_value(float(values[r]))
+        self._set_schedule_values(self.exploration_rate_schedules, eps)
+        self._set_schedule_values(self.lr_schedules, lr)
         return eps, lr
+
+    @staticmethod
+    def _set_schedule_values(schedules, values) -> None:
+        """Every distinct schedule object takes its value from the per-run array ``values``."""
+        last = {id(s): (s, r) for r, s in enumerate(schedules)}  # (a shared schedule: its runs hold the same value)
+        for s, r in last.values():
+            s.set_value(float(values[r]))
+
+    def _fetch_call(self, total, st, counts, log, with_steps) -> tuple:
+        """After the library's training or evaluation call returned ``total``: raises what it refused, keeps the statistics
+        and fetches the episode log.  Returns ``(empty, returns, steps, offsets)``; ``empty``: some run met a state without
+        a selectable action, which :meth:`_unless_empty` raises once the call's result is built."""
+        empty = total == _lib.ERR_INDEX
+        if total < 0 and not empty:
+            _lib.check(total)
+        self.last_stats = {f: getattr(st, f) for f, _ in st._fields_}
+        total = int(counts.sum())
+        rets = np.empty(total if log else 0, dtype=np.float32)
+        at = np.empty(total if log else 0, dtype=np.int32) if with_steps else None
+        if log and total:
+            _lib.check(self._lib.qe_population_log(self._h, total, _lib.ptr(at, C.c_int32), _lib.ptr(rets, C.c_float)))
+        offsets = np.zeros(self.runs + 1, dtype=np.int64)
+        if log:
+            np.cumsum(counts, out=offsets[1:])
+        return empty, rets, at, offsets
+
+    @staticmethod
+    def _unless_empty(empty, status_bits, result):
+        """``result``, or with ``empty`` the ``IndexError`` that names the runs with a bit set in ``status_bits`` (``.runs``)
+        and carries ``result`` (``.result``)."""
+        if empty:
+            bad = np.flatnonzero(status_bits).tolist()
+            err = IndexError(f"Cannot choose from an empty sequence (runs {', '.join(map(str, bad))})")
+            err.runs = bad
+            err.result = result
+            raise err
+        return result
 
     def run_steps(self, steps, env, curr_state_dict=None, log=True) -> PopulationRun:
         """``steps`` steps of every run on ``env`` (a device environment of ``num_agents == runs``).  ``curr_state_dict``
@@ -681,12 +697,9 @@ class QLearningPopulation:
             env.reset_device()
         elif not env.is_resident(curr_state_dict):
             env.restore(curr_state_dict["states"], curr_state_dict["rewards"], curr_state_dict.get("aux"))
-        if self.update_rule == "sarsa":
-            self.pending_actions = None if curr_state_dict is None else curr_state_dict.get("pending_actions")
-        if self.n_step > 1:
-            self.n_step_window = None if curr_state_dict is None else curr_state_dict.get("n_step_window")
-        if self.trace_decay is not None:
-            self.eligibility_traces = None if curr_state_dict is None else curr_state_dict.get("eligibility_traces")
+        carried = [key for key, has in _CARRIED.items() if has(self)]
+        for key in carried:
+            setattr(self, key, None if curr_state_dict is None else curr_state_dict.get(key))
         eps_d = self._descriptors(self.exploration_rate_schedules)
         lr_d = self._descriptors(self.lr_schedules)
         sched_p = C.POINTER(_lib.RunSchedule)
@@ -703,20 +716,8 @@ class QLearningPopulation:
             self._h, env.handle, steps, mode, 1 if log else 0, C.byref(st), _lib.ptr(counts, C.c_int64),
             _lib.ptr(sums, C.c_float), C.cast(base, C.POINTER(C.c_int32)), C.cast(base + 4 * M, C.POINTER(C.c_uint32)),
             C.cast(base + 8 * M, C.POINTER(C.c_float)), _lib.ptr(status, C.c_uint32))
-        empty = total == _lib.ERR_INDEX
-        if total < 0 and not empty:
-            _lib.check(total)
+        empty, rets, at, offsets = self._fetch_call(total, st, counts, log, True)
         eps_v, lr_v = self._adopt_schedule_values()
-        self.last_stats = {f: getattr(st, f) for f, _ in st._fields_}
-        total = int(counts.sum())
-        rets = np.empty(total if log else 0, dtype=np.float32)
-        at = np.empty(total if log else 0, dtype=np.int32)
-        if log and total:
-            n = self._lib.qe_population_log(self._h, total, _lib.ptr(at, C.c_int32), _lib.ptr(rets, C.c_float))
-            _lib.check(n)
-        offsets = np.zeros(M + 1, dtype=np.int64)
-        if log:
-            np.cumsum(counts, out=offsets[1:])
         with np.errstate(divide="ignore", invalid="ignore"):
             means = sums / counts.astype(np.float32)  # float32, as the standalone's float32 sum / len
         means[counts == 0] = np.nan
@@ -725,41 +726,24 @@ class QLearningPopulation:
         state_dict["rng_step"] = self._rng_step()
         state_dict["lr"] = lr_v
         state_dict["exploration_rate"] = eps_v
-        if self.update_rule == "sarsa":
-            state_dict["pending_actions"] = self.pending_actions
-        if self.n_step > 1:
-            state_dict["n_step_window"] = self.n_step_window
-        if self.trace_decay is not None:
-            state_dict["eligibility_traces"] = self.eligibility_traces
-        result = PopulationRun(means, counts, rets, offsets, at, state_dict)
-        if empty:
-            bad = np.flatnonzero(status).tolist()
-            err = IndexError(f"Cannot choose from an empty sequence (runs {', '.join(map(str, bad))})")
-            err.runs = bad
-            err.result = result
-            raise err
-        return result
+        for key in carried:
+            state_dict[key] = getattr(self, key)
+        return self._unless_empty(empty, status, PopulationRun(means, counts, rets, offsets, at, state_dict))
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
         counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``) window and (``trace_decay``) trace slots.  Tables: :meth:`load`; environments: pass
         the dict to ``run_steps``."""
-        if self.update_rule == "sarsa":
-            self.pending_actions = state_dict.get("pending_actions")
-        if self.n_step > 1:
-            self.n_step_window = state_dict.get("n_step_window")
-        if self.trace_decay is not None:
-            self.eligibility_traces = state_dict.get("eligibility_traces")
+        for key, has in _CARRIED.items():
+            if has(self):
+                setattr(self, key, state_dict.get(key))
         rng_step = state_dict["rng_step"]
         if np.ndim(rng_step) == 0:
             self.step_counter = int(rng_step)
         else:
             self.step_counters = rng_step
         for schedules, key in ((self.lr_schedules, "lr"), (self.exploration_rate_schedules, "exploration_rate")):
-            values = np.broadcast_to(np.asarray(state_dict[key], dtype=np.float64), (self.runs,))
-            last = {id(s): (s, r) for r, s in enumerate(schedules)}
-            for s, r in last.values():
-                s.set_value(float(values[r]))
+            self._set_schedule_values(schedules, np.broadcast_to(np.asarray(state_dict[key], dtype=np.float64), (self.runs,)))
 
     # ------------------------------------------------------------------ evaluation and train
     def _check_env(self, env) -> None:
@@ -847,25 +831,8 @@ class QLearningPopulation:
         total = self._lib.qe_population_evaluate(
             self._h, env.handle, steps, episodes, 1 if log else 0, C.byref(st), _lib.ptr(counts, C.c_int64),
             _lib.ptr(sums, C.c_float), _lib.ptr(used, C.c_int64), _lib.ptr(status, C.c_uint32))
-        empty = total == _lib.ERR_INDEX
-        if total < 0 and not empty:
-            _lib.check(total)
-        self.last_stats = {f: getattr(st, f) for f, _ in st._fields_}
-        total = int(counts.sum())
-        rets = np.empty(total if log else 0, dtype=np.float32)
-        if log and total:
-            _lib.check(self._lib.qe_population_log(self._h, total, None, _lib.ptr(rets, C.c_float)))
-        offsets = np.zeros(M + 1, dtype=np.int64)
-        if log:
-            np.cumsum(counts, out=offsets[1:])
-        result = PopulationEval(sums, counts, rets, offsets, used, (status & 2) == 0)
-        if empty:
-            bad = np.flatnonzero(status & 1).tolist()
-            err = IndexError(f"Cannot choose from an empty sequence (runs {', '.join(map(str, bad))})")
-            err.runs = bad
-            err.result = result
-            raise err
-        return result
+        empty, rets, _, offsets = self._fetch_call(total, st, counts, log, False)
+        return self._unless_empty(empty, status & 1, PopulationEval(sums, counts, rets, offsets, used, (status & 2) == 0))
 
     def train(self, env, steps, val_env, val_every_n_steps, val_steps=None, val_episodes=None, curr_state_dict=None,
               max_val_steps=None) -> PopulationTraining:

@@ -167,19 +167,28 @@ struct PopState {
     DevBuf<uint32_t> status;           // per run, per call: 1 = some step found no selectable action
     DevBuf<long long> ep_count;        // per run, per call: episodes ended ...
     DevBuf<float> ep_sum;              // ... and the float32 sequential sum of their returns
-    DevBuf<int32_t> seg_cnt, seg_step, off, out_step;  // episode log: per-run segments of a launch, compacted copy
-    DevBuf<float> seg_ret, out_ret;
-    PinnedBuf<int32_t> h_cnt, h_step;
-    PinnedBuf<float> h_ret;
-    std::vector<int32_t> log_step;     // episode log of the latest call in (run, episode) order
-    std::vector<float> log_ret;
+    struct EpisodeLog {
+        DevBuf<int32_t> seg_cnt, seg_step, off, out_step;  // per-run segments of a launch, compacted copy
+        DevBuf<float> seg_ret, out_ret;
+        PinnedBuf<int32_t> h_cnt, h_step;
+        PinnedBuf<float> h_ret;
+        std::vector<int32_t> step;     // episode log of the latest call in (run, episode) order
+        std::vector<float> ret;
+        void release() {
+            seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
+            h_cnt.release(); h_step.release(); h_ret.release();
+        }
+    } log;
     // Per-run draw counters: run r's next step is qe_engine::step_ctr + step_off[r].  step_off is only read while
     // off_any (some offset is non-zero: an episode-based evaluation ended the runs after different step counts).
     DevBuf<unsigned long long> step_off;
     bool off_any = false;
-    DevBuf<long long> used;            // greedy evaluation, episode mode: steps each run took in the call ...
-    DevBuf<uint8_t> done;              // ... and whether it has reached its episode count
-    PinnedBuf<uint8_t> h_done;
+    struct EpisodeMode {               // greedy evaluation, episode mode
+        DevBuf<long long> used;        // steps each run took in the call ...
+        DevBuf<uint8_t> done;          // ... and whether it has reached its episode count
+        PinnedBuf<uint8_t> h_done;
+        void release() { used.release(); done.release(); h_done.release(); }
+    } epi;
     // Update rule of every run (qe_update_rule).  SARSA carries the action chosen for a run's next step from launch to
     // launch and call to call: pending[r], -1 = none (allocated on first use; k_rollout_runs_td, qe_rollout_runs_td.h).
     int rule = QE_RULE_Q_LEARNING;
@@ -187,40 +196,51 @@ struct PopState {
     // Double estimator (qe_population_set_double): table B, the engine's dtype, shape and row stride; the engine's own
     // table is A.  NULL: off (k_double_rollout / k_double_evaluate, qe_rollout_double.h).
     void* table_b = nullptr;
-    // n-step rules (qe_population_set_n_step): the horizon, 1 = the one-step kernels above.  n_step > 1: every run's
-    // window of at most n_step - 1 transitions between launches, [slot][runs], oldest first (k_nstep_rollout,
-    // qe_rollout_nstep.h); allocated when n_step is set.
-    int n_step = 1;
-    DevBuf<int32_t> win_len, win_s, win_a;
-    DevBuf<float> win_r;
-    // Eligibility traces (qe_population_set_traces): trace_k slots per run, 0 = off (the kernels above).  On: every
-    // run's slots between launches, [slot][runs] (trace_e holds trace_k * runs values of the table dtype; a slot whose
-    // value is 0 is free), and every run's lambda (k_trace_rollout, qe_rollout_trace.h); allocated when traces are set.
-    int trace_k = 0, trace_kind = 0;
-    DevBuf<int32_t> trace_s, trace_a;
-    DevBuf<double> trace_e;
-    DevBuf<double> trace_lambda;
-    std::vector<double> h_lambda;
+    // n-step rules (qe_population_set_n_step): the horizon, 1 = the one-step kernels above.  n > 1: every run's
+    // window of at most n - 1 transitions between launches, [slot][runs], oldest first (k_nstep_rollout,
+    // qe_rollout_nstep.h); allocated when the horizon is set.
+    struct Window {
+        int n = 1;
+        DevBuf<int32_t> len, s, a;
+        DevBuf<float> r;
+        void release() {
+            len.release(); s.release(); a.release(); r.release();
+            n = 1;
+        }
+    } win;
+    // Eligibility traces (qe_population_set_traces): k slots per run, 0 = off (the kernels above).  On: every run's
+    // slots between launches, [slot][runs] (e holds k * runs values of the table dtype; a slot whose value is 0 is
+    // free), and every run's lambda (k_trace_rollout, qe_rollout_trace.h); allocated when traces are set.
+    struct Traces {
+        int k = 0, kind = 0;
+        DevBuf<int32_t> s, a;
+        DevBuf<double> e;
+        DevBuf<double> lambda;
+        std::vector<double> h_lambda;
+        void release() {
+            s.release(); a.release(); e.release(); lambda.release();
+            h_lambda.clear();
+            k = 0;
+        }
+    } trace;
     // Dyna-Q (qe_population_set_planning): planning updates per step, 0 = off (the kernels above).  On: every run's
     // learned model, one 8-byte entry per table cell ([runs][S * ld]: next_obs | terminated << 31 or 0xFFFFFFFF = unseen,
     // then the reward's bits), the table offsets of its seen cells in order of first observation ([runs][S * A]) and their
     // count (k_dyna_rollout, qe_rollout_dyna.h); allocated when planning is set, kept until it is set to 0.
-    int planning = 0;
-    DevBuf<uint2> dyna_entry;
-    DevBuf<int32_t> dyna_visited, dyna_count;
+    struct Model {
+        int planning = 0;
+        DevBuf<uint2> entry;
+        DevBuf<int32_t> visited, count;
+        void release() {
+            entry.release(); visited.release(); count.release();
+            planning = 0;
+        }
+    } dyna;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
-        seg_cnt.release(); seg_step.release(); off.release(); out_step.release(); seg_ret.release(); out_ret.release();
-        h_cnt.release(); h_step.release(); h_ret.release();
-        step_off.release(); used.release(); done.release(); h_done.release(); pending.release();
-        win_len.release(); win_s.release(); win_a.release(); win_r.release();
-        n_step = 1;
-        trace_s.release(); trace_a.release(); trace_e.release(); trace_lambda.release();
-        h_lambda.clear();
-        trace_k = 0;
-        dyna_entry.release(); dyna_visited.release(); dyna_count.release();
-        planning = 0;
+        log.release(); epi.release(); win.release(); trace.release(); dyna.release();
+        step_off.release(); pending.release();
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
         off_any = false;
@@ -470,7 +490,19 @@ template <typename T, class Env>
 int launch_stepwise(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, bool turn);
 template <typename T, class Env>
 int launch_eval(qe_engine* e, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps);
-// The (NV, masked) build of a population kernel for a row stride (qe_inst_runs.hip, qe_inst_runs_td.hip, qe_inst_runs_double.hip, qe_inst_runs_nstep.hip, qe_inst_runs_trace.hip, qe_inst_runs_dyna.hip): go(integral_constant<int, NV>, bool_constant<masked>).
+// What every launch of a population kernel takes: the stream, the runs and the environment, the row stride and mask
+// build that pick the instantiation, and the steps of this launch.
+template <typename T>
+struct RunsLaunch {
+    hipStream_t stream;
+    RunsCtx<T> c;
+    EnvCtx ev;
+    int ld;
+    bool masked;
+    long long steps;
+};
+
+// The (NV, masked) build of a population kernel for a row stride (the qe_inst_runs*.hip units): go(integral_constant<int, NV>, bool_constant<masked>).
 template <class Env, class F>
 inline int64_t runs_by_build(int ld, bool masked, F go) {
     using Yes = std::true_type;
@@ -491,37 +523,40 @@ inline int64_t runs_by_build(int ld, bool masked, F go) {
     }
 }
 
-// population path: one launch of `steps` steps of every run (qe_inst_runs.hip); returns its kernel_variant
+// One launch of the population kernel of `path` (QE_VARIANT_RUNS*): go(nv, mk, grid, block) launches its (NV, masked)
+// build and returns the variant bits of its own (0: none); returns the launch's kernel_variant.
+template <class Env, typename T, class F>
+inline int64_t launch_runs_build(const RunsLaunch<T>& l, int64_t path, F go) {
+    const dim3 grid(grid_for(l.c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
+    return runs_by_build<Env>(l.ld, l.masked, [&](auto nv, auto mk) -> int64_t {
+        return path | go(nv, mk, grid, block) | ((int64_t)decltype(nv)::value << 12) | ((int64_t)decltype(mk)::value << 20);
+    });
+}
+
+// population path: one launch of l.steps steps of every run (qe_inst_runs.hip); returns its kernel_variant
 template <typename T, class Env>
-int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps);
+int64_t launch_runs(const RunsLaunch<T>& l);
 // ... with the update rule `rule` (QE_RULE_SARSA: `pending` holds every run's pending action; QE_RULE_EXPECTED_SARSA),
 // qe_inst_runs_td.hip; a build the rule is not compiled for returns QE_ERR_UNSUPPORTED (see runs_td_supported)
 template <typename T, class Env>
-int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                       int32_t* pending);
+int64_t launch_runs_td(const RunsLaunch<T>& l, int rule, int32_t* pending);
 // ... with the n-step form of that rule and the runs' windows `w` (qe_inst_runs_nstep.hip)
 template <typename T, class Env>
-int64_t launch_nstep_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                          int32_t* pending, const NStepWin& w);
+int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const NStepWin& w);
 // ... with eligibility traces: `rule` is QE_RULE_Q_LEARNING or QE_RULE_SARSA, `w` the runs' slots (qe_inst_runs_trace.hip)
 template <typename T, class Env>
-int64_t launch_trace_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                          int32_t* pending, const TraceSlots<T>& w);
+int64_t launch_trace_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const TraceSlots<T>& w);
 // ... with Dyna-Q: Q-learning's step, then w.n planning updates from the runs' learned models (qe_inst_runs_dyna.hip)
 template <typename T, class Env>
-int64_t launch_dyna_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                         const DynaModel& w);
+int64_t launch_dyna_runs(const RunsLaunch<T>& l, const DynaModel& w);
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
-int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                             long long episodes, long long* used, uint8_t* done);
-// ... and the double estimator (qe_inst_runs_double.hip): training and greedy evaluation over the tables c.q and table_b
+int64_t launch_evaluate_runs(const RunsLaunch<T>& l, long long episodes, long long* used, uint8_t* done);
+// ... and the double estimator (qe_inst_runs_double.hip): training and greedy evaluation over the tables l.c.q and table_b
 template <typename T, class Env>
-int64_t launch_double_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                           T* table_b);
+int64_t launch_double_runs(const RunsLaunch<T>& l, T* table_b);
 template <typename T, class Env>
-int64_t launch_double_evaluate(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                               long long episodes, long long* used, uint8_t* done, const T* table_b);
+int64_t launch_double_evaluate(const RunsLaunch<T>& l, long long episodes, long long* used, uint8_t* done, const T* table_b);
 // resident workgroups per CU of the k_step_turn build this engine would launch (occupancy query), 0 on failure
 template <typename T, class Env>
 int turn_occupancy(const qe_engine* e);

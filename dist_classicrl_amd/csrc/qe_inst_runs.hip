@@ -8,31 +8,23 @@
 #error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
 #endif
 
-// One launch of `steps` steps of every run; returns the kernel_variant of the build (QE_VARIANT_RUNS | NV | masked).
+// One launch of l.steps steps of every run; returns the kernel_variant of the build (QE_VARIANT_RUNS | NV | masked).
 template <typename T, class Env>
-int64_t launch_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
-        hipLaunchKernelGGL((k_rollout_runs<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps);
-        return QE_VARIANT_RUNS | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+int64_t launch_runs(const RunsLaunch<T>& l) {
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
+        hipLaunchKernelGGL((k_rollout_runs<T, Env, decltype(nv)::value, decltype(mk)::value>), grid, block, 0, l.stream, l.c, l.ev, l.steps);
+        return 0;
     });
 }
 
 // One launch of greedy evaluation (k_evaluate_runs); returns QE_VARIANT_RUNS_EVAL | NV | masked.
 template <typename T, class Env>
-int64_t launch_evaluate_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                             long long episodes, long long* used, uint8_t* done) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
-        hipLaunchKernelGGL((k_evaluate_runs<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps, episodes, used, done);
-        return QE_VARIANT_RUNS_EVAL | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+int64_t launch_evaluate_runs(const RunsLaunch<T>& l, long long episodes, long long* used, uint8_t* done) {
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_EVAL, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
+        hipLaunchKernelGGL((k_evaluate_runs<T, Env, decltype(nv)::value, decltype(mk)::value>), grid, block, 0, l.stream, l.c, l.ev, l.steps, episodes, used, done);
+        return 0;
     });
 }
 
-template int64_t launch_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool, long long);
-template int64_t launch_evaluate_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool,
-                                                              long long, long long, long long*, uint8_t*);
+template int64_t launch_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&);
+template int64_t launch_evaluate_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, long long, long long*, uint8_t*);

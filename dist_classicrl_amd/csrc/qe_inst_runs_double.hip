@@ -8,34 +8,25 @@
 #error "compile with -DQE_INST_T=<float|double> -DQE_INST_ENV=<HashEnv|GridEnv|BanditEnv|TttEnv|TableEnv>"
 #endif
 
-// One launch of `steps` steps of every run, second table `table_b`; returns QE_VARIANT_RUNS_DOUBLE | NV | masked.
+// One launch of l.steps steps of every run, second table `table_b`; returns QE_VARIANT_RUNS_DOUBLE | NV | masked.
 template <typename T, class Env>
-int64_t launch_double_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                           T* table_b) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
-        hipLaunchKernelGGL((k_double_rollout<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps, table_b);
-        return QE_VARIANT_RUNS_DOUBLE | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+int64_t launch_double_runs(const RunsLaunch<T>& l, T* table_b) {
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_DOUBLE, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
+        hipLaunchKernelGGL((k_double_rollout<T, Env, decltype(nv)::value, decltype(mk)::value>), grid, block, 0, l.stream, l.c, l.ev, l.steps, table_b);
+        return 0;
     });
 }
 
 // One launch of its greedy evaluation (k_double_evaluate); returns QE_VARIANT_RUNS_DOUBLE_EVAL | NV | masked.
 template <typename T, class Env>
-int64_t launch_double_evaluate(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps,
-                               long long episodes, long long* used, uint8_t* done, const T* table_b) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
-        hipLaunchKernelGGL((k_double_evaluate<T, Env, NV, MK>), grid, block, 0, stream, c, ev, steps, episodes, used, done,
+int64_t launch_double_evaluate(const RunsLaunch<T>& l, long long episodes, long long* used, uint8_t* done, const T* table_b) {
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_DOUBLE_EVAL, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
+        hipLaunchKernelGGL((k_double_evaluate<T, Env, decltype(nv)::value, decltype(mk)::value>), grid, block, 0, l.stream, l.c, l.ev, l.steps, episodes, used, done,
                            table_b);
-        return QE_VARIANT_RUNS_DOUBLE_EVAL | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+        return 0;
     });
 }
 
-template int64_t launch_double_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool,
-                                                            long long, QE_INST_T*);
-template int64_t launch_double_evaluate<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool,
-                                                                long long, long long, long long*, uint8_t*, const QE_INST_T*);
+template int64_t launch_double_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, QE_INST_T*);
+template int64_t launch_double_evaluate<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, long long, long long*, uint8_t*,
+                                                                const QE_INST_T*);

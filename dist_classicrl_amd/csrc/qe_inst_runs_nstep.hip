@@ -12,24 +12,19 @@ static_assert((int)QE_RULE_SARSA == (int)TD_SARSA && (int)QE_RULE_EXPECTED_SARSA
               "qe_update_rule and TdRule differ");
 static_assert(NSTEP_MAX < 32, "kernel_variant carries n in five bits");
 
-// One launch of `steps` steps of every run under `rule` with the windows `w`; the window of a workgroup is dynamic LDS.
+// One launch of l.steps steps of every run under `rule` with the windows `w`; the window of a workgroup is dynamic LDS.
 // Returns QE_VARIANT_RUNS_NSTEP | rule | NV | masked | n.
 template <typename T, class Env>
-int64_t launch_nstep_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                          int32_t* pending, const NStepWin& w) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
+int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const NStepWin& w) {
     const size_t lds = nstep_lds_bytes(w.n);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_NSTEP, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
         if (rule == QE_RULE_SARSA)
-            hipLaunchKernelGGL((k_nstep_rollout<T, Env, NV, MK, TD_SARSA>), grid, block, lds, stream, c, ev, steps, pending, w);
+            hipLaunchKernelGGL((k_nstep_rollout<T, Env, decltype(nv)::value, decltype(mk)::value, TD_SARSA>), grid, block, lds, l.stream, l.c, l.ev, l.steps, pending, w);
         else
-            hipLaunchKernelGGL((k_nstep_rollout<T, Env, NV, MK, TD_EXPECTED_SARSA>), grid, block, lds, stream, c, ev, steps,
+            hipLaunchKernelGGL((k_nstep_rollout<T, Env, decltype(nv)::value, decltype(mk)::value, TD_EXPECTED_SARSA>), grid, block, lds, l.stream, l.c, l.ev, l.steps,
                                pending, w);
-        return QE_VARIANT_RUNS_NSTEP | ((int64_t)rule << 4) | ((int64_t)NV << 12) | ((int64_t)MK << 20) | ((int64_t)w.n << 24);
+        return ((int64_t)rule << 4) | ((int64_t)w.n << 24);
     });
 }
 
-template int64_t launch_nstep_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool,
-                                                           long long, int, int32_t*, const NStepWin&);
+template int64_t launch_nstep_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, int, int32_t*, const NStepWin&);

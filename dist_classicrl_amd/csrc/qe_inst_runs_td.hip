@@ -11,22 +11,17 @@
 static_assert((int)QE_RULE_SARSA == (int)TD_SARSA && (int)QE_RULE_EXPECTED_SARSA == (int)TD_EXPECTED_SARSA,
               "qe_update_rule and TdRule differ");
 
-// One launch of `steps` steps of every run under `rule`; returns QE_VARIANT_RUNS_TD | rule | NV | masked.
+// One launch of l.steps steps of every run under `rule`; returns QE_VARIANT_RUNS_TD | rule | NV | masked.
 template <typename T, class Env>
-int64_t launch_runs_td(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                       int32_t* pending) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
+int64_t launch_runs_td(const RunsLaunch<T>& l, int rule, int32_t* pending) {
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_TD, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
         if (rule == QE_RULE_SARSA)
-            hipLaunchKernelGGL((k_rollout_runs_td<T, Env, NV, MK, TD_SARSA>), grid, block, 0, stream, c, ev, steps, pending);
+            hipLaunchKernelGGL((k_rollout_runs_td<T, Env, decltype(nv)::value, decltype(mk)::value, TD_SARSA>), grid, block, 0, l.stream, l.c, l.ev, l.steps, pending);
         else
-            hipLaunchKernelGGL((k_rollout_runs_td<T, Env, NV, MK, TD_EXPECTED_SARSA>), grid, block, 0, stream, c, ev, steps,
+            hipLaunchKernelGGL((k_rollout_runs_td<T, Env, decltype(nv)::value, decltype(mk)::value, TD_EXPECTED_SARSA>), grid, block, 0, l.stream, l.c, l.ev, l.steps,
                                pending);
-        return QE_VARIANT_RUNS_TD | ((int64_t)rule << 4) | ((int64_t)NV << 12) | ((int64_t)MK << 20);
+        return (int64_t)rule << 4;
     });
 }
 
-template int64_t launch_runs_td<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool, long long,
-                                                        int, int32_t*);
+template int64_t launch_runs_td<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, int, int32_t*);

@@ -13,25 +13,19 @@ static_assert((int)QE_TRACE_REPLACING == (int)TRACE_REPLACING && (int)QE_TRACE_A
               "qe_trace_kind and TraceKind differ");
 static_assert(TRACE_MAX < 64, "kernel_variant carries K in six bits");
 
-// One launch of `steps` steps of every run under `rule` with the trace slots `w`; the slots of a workgroup are dynamic
+// One launch of l.steps steps of every run under `rule` with the trace slots `w`; the slots of a workgroup are dynamic
 // LDS.  Returns QE_VARIANT_RUNS_TRACE | rule | NV | masked | K | kind.
 template <typename T, class Env>
-int64_t launch_trace_runs(hipStream_t stream, const RunsCtx<T>& c, const EnvCtx& ev, int ld, bool masked, long long steps, int rule,
-                          int32_t* pending, const TraceSlots<T>& w) {
-    const dim3 grid(grid_for(c.M, RUNS_BLOCK)), block(RUNS_BLOCK);
+int64_t launch_trace_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const TraceSlots<T>& w) {
     const size_t lds = trace_lds_bytes(w.K, sizeof(T));
-    return runs_by_build<Env>(ld, masked, [&](auto nv, auto mk) -> int64_t {
-        constexpr int NV = decltype(nv)::value;
-        constexpr bool MK = decltype(mk)::value;
+    return launch_runs_build<Env>(l, QE_VARIANT_RUNS_TRACE, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
         if (rule == QE_RULE_SARSA)
-            hipLaunchKernelGGL((k_trace_rollout<T, Env, NV, MK, TD_SARSA>), grid, block, lds, stream, c, ev, steps, pending, w);
+            hipLaunchKernelGGL((k_trace_rollout<T, Env, decltype(nv)::value, decltype(mk)::value, TD_SARSA>), grid, block, lds, l.stream, l.c, l.ev, l.steps, pending, w);
         else
-            hipLaunchKernelGGL((k_trace_rollout<T, Env, NV, MK, TD_Q_LEARNING>), grid, block, lds, stream, c, ev, steps, pending,
+            hipLaunchKernelGGL((k_trace_rollout<T, Env, decltype(nv)::value, decltype(mk)::value, TD_Q_LEARNING>), grid, block, lds, l.stream, l.c, l.ev, l.steps, pending,
                                w);
-        return QE_VARIANT_RUNS_TRACE | ((int64_t)rule << 4) | ((int64_t)NV << 12) | ((int64_t)MK << 20) | ((int64_t)w.K << 24) |
-               ((int64_t)w.kind << 30);
+        return ((int64_t)rule << 4) | ((int64_t)w.K << 24) | ((int64_t)w.kind << 30);
     });
 }
 
-template int64_t launch_trace_runs<QE_INST_T, QE_INST_ENV>(hipStream_t, const RunsCtx<QE_INST_T>&, const EnvCtx&, int, bool,
-                                                           long long, int, int32_t*, const TraceSlots<QE_INST_T>&);
+template int64_t launch_trace_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, int, int32_t*, const TraceSlots<QE_INST_T>&);

@@ -1,16 +1,7 @@
 // qe_population.hip -- host side of the population path (include/qlearn_engine.h, "population"): M independent
-// single-agent runs in one [M * S, ld] table, trained by k_rollout_runs (Q-learning) or k_rollout_runs_td (SARSA, Expected
-// SARSA: qe_rollout_runs_td.h, instantiated in qe_inst_runs_td.hip) and evaluated greedily by k_evaluate_runs
-// (qe_rollout_runs.h, instantiated in qe_inst_runs.hip), plus the compaction of the per-run episode-log segments and
-// the per-run draw counters.  With the double estimator on (qe_population_set_double) a second table B of the same
-// shape stands beside the engine's table A: k_double_rollout trains both and k_double_evaluate acts on their sum
-// (qe_rollout_double.h, instantiated in qe_inst_runs_double.hip).  With a horizon n > 1 (qe_population_set_n_step) the
-// on-policy rules train through k_nstep_rollout (qe_rollout_nstep.h, instantiated in qe_inst_runs_nstep.hip), which
-// carries every run's window of transitions from launch to launch in the win_* arrays.  With eligibility traces on
-// (qe_population_set_traces) SARSA and Q-learning train through k_trace_rollout (qe_rollout_trace.h, instantiated in
-// qe_inst_runs_trace.hip), which carries every run's trace slots from launch to launch in the trace_* arrays.  With
-// planning on (qe_population_set_planning) Q-learning trains through k_dyna_rollout (qe_rollout_dyna.h, instantiated in
-// qe_inst_runs_dyna.hip), which keeps every run's learned model and visited list in the dyna_* arrays.
+// single-agent runs in one [M * S, ld] table.  Which kernel trains them is launch_training's to say, what each method
+// carries between launches and calls is PopState's (qe_host.h); the two calls share one skeleton (PopCall), which cuts
+// them into launches, compacts the per-run episode-log segments and reports.  The per-run draw counters live here too.
 #include "qe_host.h"
 #include "qe_rollout_dyna.h"
 #include "qe_rollout_nstep.h"
@@ -89,10 +80,10 @@ long long launch_len(int64_t M, int64_t steps, bool log, int planning = 0) {
     return per_launch;
 }
 
-int log_reserve(PopState& P, size_t m, long long per_launch) {
+int log_reserve(PopState::EpisodeLog& G, size_t m, long long per_launch) {
     const size_t seg = m * (size_t)per_launch;
-    HIP_TRY(P.seg_cnt.ensure(m)); HIP_TRY(P.off.ensure(m + 1)); HIP_TRY(P.seg_step.ensure(seg)); HIP_TRY(P.seg_ret.ensure(seg));
-    HIP_TRY(P.out_step.ensure(seg)); HIP_TRY(P.out_ret.ensure(seg)); HIP_TRY(P.h_cnt.ensure(m + 1));
+    HIP_TRY(G.seg_cnt.ensure(m)); HIP_TRY(G.off.ensure(m + 1)); HIP_TRY(G.seg_step.ensure(seg)); HIP_TRY(G.seg_ret.ensure(seg));
+    HIP_TRY(G.out_step.ensure(seg)); HIP_TRY(G.out_ret.ensure(seg)); HIP_TRY(G.h_cnt.ensure(m + 1));
     return QE_OK;
 }
 
@@ -104,43 +95,42 @@ struct CallLog {
 
 // Compacts the segments the launch of `k` steps has just written and appends them to `L` (synchronises the stream).
 int log_launch(qe_engine* e, long long k, CallLog& L, int64_t& launches) {
-    PopState& P = e->pop;
-    const int64_t M = P.runs;
+    PopState::EpisodeLog& G = e->pop.log;
+    const int64_t M = e->pop.runs;
     const size_t m = (size_t)M;
-    hipLaunchKernelGGL(k_runs_log_scan, dim3(1), dim3(1024), 0, e->stream, (const int32_t*)P.seg_cnt.p, M, P.off.p);
-    hipLaunchKernelGGL(k_runs_log_pack, dim3(grid_for(M, 256)), dim3(256), 0, e->stream, (const int32_t*)P.seg_cnt.p,
-                       (const int32_t*)P.off.p, (const int32_t*)P.seg_step.p, (const float*)P.seg_ret.p, k, M,
-                       P.out_step.p, P.out_ret.p);
+    hipLaunchKernelGGL(k_runs_log_scan, dim3(1), dim3(1024), 0, e->stream, (const int32_t*)G.seg_cnt.p, M, G.off.p);
+    hipLaunchKernelGGL(k_runs_log_pack, dim3(grid_for(M, 256)), dim3(256), 0, e->stream, (const int32_t*)G.seg_cnt.p,
+                       (const int32_t*)G.off.p, (const int32_t*)G.seg_step.p, (const float*)G.seg_ret.p, k, M,
+                       G.out_step.p, G.out_ret.p);
     launches += 2;
-    HIP_TRY(hipMemcpyAsync(P.h_cnt.p, P.seg_cnt.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.h_cnt.p + m, P.off.p + m, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(G.h_cnt.p, G.seg_cnt.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(G.h_cnt.p + m, G.off.p + m, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    const size_t total = (size_t)P.h_cnt.p[m];
-    L.cnt.insert(L.cnt.end(), P.h_cnt.p, P.h_cnt.p + m);
+    const size_t total = (size_t)G.h_cnt.p[m];
+    L.cnt.insert(L.cnt.end(), G.h_cnt.p, G.h_cnt.p + m);
     if (total) {
-        HIP_TRY(P.h_step.ensure(total)); HIP_TRY(P.h_ret.ensure(total));
-        HIP_TRY(hipMemcpyAsync(P.h_step.p, P.out_step.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(P.h_ret.p, P.out_ret.p, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(G.h_step.ensure(total)); HIP_TRY(G.h_ret.ensure(total));
+        HIP_TRY(hipMemcpyAsync(G.h_step.p, G.out_step.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(G.h_ret.p, G.out_ret.p, total * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        L.step.insert(L.step.end(), P.h_step.p, P.h_step.p + total);
-        L.ret.insert(L.ret.end(), P.h_ret.p, P.h_ret.p + total);
+        L.step.insert(L.step.end(), G.h_step.p, G.h_step.p + total);
+        L.ret.insert(L.ret.end(), G.h_ret.p, G.h_ret.p + total);
     }
     return QE_OK;
 }
 
-// Launch-major -> (run, episode) order, into P.log_step / P.log_ret (qe_population_log).
-void log_finish(PopState& P, const CallLog& L, const std::vector<long long>& counts) {
-    const size_t m = (size_t)P.runs;
+// Launch-major -> (run, episode) order, into G.step / G.ret (qe_population_log).
+void log_finish(PopState::EpisodeLog& G, size_t m, const CallLog& L, const std::vector<long long>& counts) {
     std::vector<size_t> at(m + 1, 0);
     for (size_t r = 0; r < m; ++r) at[r + 1] = at[r] + (size_t)counts[r];
-    P.log_step.resize(L.step.size());
-    P.log_ret.resize(L.ret.size());
+    G.step.resize(L.step.size());
+    G.ret.resize(L.ret.size());
     size_t src = 0;
     for (size_t l = 0; l < L.cnt.size() / std::max<size_t>(m, 1); ++l)
         for (size_t r = 0; r < m; ++r)
             for (int32_t j = 0; j < L.cnt[l * m + r]; ++j, ++src) {
-                P.log_step[at[r]] = L.step[src];
-                P.log_ret[at[r]] = L.ret[src];
+                G.step[at[r]] = L.step[src];
+                G.ret[at[r]] = L.ret[src];
                 ++at[r];
             }
 }
@@ -204,10 +194,10 @@ int pending_reserve(qe_engine* e) {
 
 // The n-step rules' windows, [slot][runs] with n - 1 slots: allocated for the horizon `n`, every window empty.
 int window_reserve(qe_engine* e, int n) {
-    PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, cells = m * (size_t)(n - 1);
-    HIP_TRY(P.win_len.ensure(m)); HIP_TRY(P.win_s.ensure(cells)); HIP_TRY(P.win_a.ensure(cells)); HIP_TRY(P.win_r.ensure(cells));
-    HIP_TRY(hipMemsetAsync(P.win_len.p, 0, m * sizeof(int32_t), e->stream));
+    PopState::Window& W = e->pop.win;
+    const size_t m = (size_t)e->pop.runs, cells = m * (size_t)(n - 1);
+    HIP_TRY(W.len.ensure(m)); HIP_TRY(W.s.ensure(cells)); HIP_TRY(W.a.ensure(cells)); HIP_TRY(W.r.ensure(cells));
+    HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
@@ -231,11 +221,11 @@ int check_trace_decay(const qe_engine* e, const double* gamma, const double* lam
 
 // Every trace slot of every run free.
 int traces_clear(qe_engine* e) {
-    PopState& P = e->pop;
-    const size_t cells = (size_t)P.runs * (size_t)P.trace_k;
-    HIP_TRY(hipMemsetAsync(P.trace_s.p, 0, cells * sizeof(int32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(P.trace_a.p, 0, cells * sizeof(int32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(P.trace_e.p, 0, cells * sizeof(double), e->stream));
+    PopState::Traces& X = e->pop.trace;
+    const size_t cells = (size_t)e->pop.runs * (size_t)X.k;
+    HIP_TRY(hipMemsetAsync(X.s.p, 0, cells * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(X.a.p, 0, cells * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(X.e.p, 0, cells * sizeof(double), e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
@@ -244,8 +234,8 @@ int traces_clear(qe_engine* e) {
 int model_clear(qe_engine* e) {
     PopState& P = e->pop;
     const size_t m = (size_t)P.runs;
-    HIP_TRY(hipMemsetAsync(P.dyna_entry.p, 0xFF, m * (size_t)P.S * (size_t)e->ld * sizeof(uint2), e->stream));  // DYNA_UNSEEN
-    HIP_TRY(hipMemsetAsync(P.dyna_count.p, 0, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.dyna.entry.p, 0xFF, m * (size_t)P.S * (size_t)e->ld * sizeof(uint2), e->stream));  // DYNA_UNSEEN
+    HIP_TRY(hipMemsetAsync(P.dyna.count.p, 0, m * sizeof(int32_t), e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
@@ -260,6 +250,152 @@ int on_table_b(qe_engine* e, F f) {
     const int rc = f();
     e->q = a;
     return rc;
+}
+
+// Slot-major state (windows, trace slots) is [slot][runs] on the device and [runs][slot] at the ABI.  These copy the
+// slots `keep(r, i)` names from one order to the other; the others become 0.  A NULL `abi` is not written.
+template <typename U, typename V, class Keep>
+void slots_to_abi(const U* dev, V* abi, size_t m, size_t w, Keep keep) {
+    for (size_t r = 0; abi && r < m; ++r)
+        for (size_t i = 0; i < w; ++i) abi[r * w + i] = keep(r, i) ? (V)dev[i * m + r] : V{};
+}
+template <typename U, typename V, class Keep>
+void slots_to_device(const V* abi, U* dev, size_t m, size_t w, Keep keep) {
+    for (size_t r = 0; r < m; ++r)
+        for (size_t i = 0; i < w; ++i) dev[i * m + r] = keep(r, i) ? (U)abi[r * w + i] : U{};
+}
+
+// The training launch of a population: the kernel of the first method that is on, in this order.
+template <typename T, class Env>
+int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
+    const PopState& P = e->pop;
+    if (P.table_b) return launch_double_runs<T, Env>(l, (T*)P.table_b);
+    if (P.dyna.planning)
+        return launch_dyna_runs<T, Env>(l, DynaModel{P.dyna.planning, P.dyna.entry.p, P.dyna.visited.p, P.dyna.count.p, P.S * (int64_t)e->A});
+    if (P.trace.k)
+        return launch_trace_runs<T, Env>(l, P.rule, P.pending.p,
+                                         TraceSlots<T>{P.trace.k, P.trace.kind, P.trace.s.p, P.trace.a.p, (T*)P.trace.e.p, P.trace.lambda.p});
+    if (P.win.n > 1) return launch_nstep_runs<T, Env>(l, P.rule, P.pending.p, NStepWin{P.win.n, P.win.len.p, P.win.s.p, P.win.a.p, P.win.r.p});
+    if (P.rule != QE_RULE_Q_LEARNING) return launch_runs_td<T, Env>(l, P.rule, P.pending.p);
+    return launch_runs<T, Env>(l);
+}
+
+// A call of qe_population_rollout / qe_population_evaluate from call_begin to call_end.
+struct PopCall {
+    qe_engine* e;
+    qe_env* env;
+    int64_t steps;
+    bool log;
+    int nan_select;   // the caller's selection rule (rollout_ctx)
+    int64_t variant;  // kernel_variant of the latest launch; of a call without one, the caller's
+    long long per_launch = 0;
+    EnvCtx ev{};
+    CallLog L;
+    int64_t launches = 0;
+    std::vector<uint32_t> st;  // every run's status, once call_end has copied it back
+};
+
+// What both calls refuse first.  The log of the previous call is gone once the engine is known to be a population.
+int call_check(qe_engine* e, const qe_env* env, int64_t steps, qe_rollout_stats* stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (int rc = need_population(e)) return rc;
+    e->pop.log.step.clear();
+    e->pop.log.ret.clear();
+    if (!env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
+    if (steps < 0) return qe_fail(QE_ERR_INVALID, "steps must be >= 0");
+    return QE_OK;
+}
+
+// The entry of a call that has passed its checks: sizes the launches (`planning`: see launch_len), reserves the log
+// buffers and, through `own_buffers`, what the caller keeps per run, zeroes the accumulators and starts the clock.
+template <class F>
+int call_begin(PopCall& c, int planning, F own_buffers) {
+    qe_engine* e = c.e;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    if (e->ld > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions");
+    HIP_TRY(hipSetDevice(e->device));
+    c.per_launch = launch_len(P.runs, c.steps, c.log, planning);
+    if (c.log)
+        if (int rc = log_reserve(P.log, m, c.per_launch)) return rc;
+    if (int rc = own_buffers()) return rc;
+    c.env->mirror_obs = nullptr; c.env->mirror_aux = nullptr; c.env->mirror_acc = nullptr;  // the device state moves on
+    HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
+    HIP_TRY(hipMemsetAsync(P.ep_sum.p, 0, m * sizeof(float), e->stream));
+    c.ev = make_envctx(e, c.env);
+    HIP_TRY(hipEventRecord(P.ev0, e->stream));
+    return QE_OK;
+}
+
+// One launch of `k` steps from step `t` of the call: `own(l, Env{})` completes l.c and launches, the rest is bookkeeping.
+template <class F>
+int call_launch(PopCall& c, long long t, long long k, F own) {
+    qe_engine* e = c.e;
+    qe_env* env = c.env;
+    PopState& P = e->pop;
+    const int64_t v = by_env(env->p.kind, [&](auto tag) -> int64_t {
+        auto go = [&](auto tt) -> int64_t {
+            using T = decltype(tt);
+            RunsLaunch<T> l{e->stream, {}, c.ev, e->ld, env->p.masked != 0, k};
+            RunsCtx<T>& x = l.c;
+            x.q = (T*)e->q; x.S = P.S; x.M = P.runs;
+            x.obs = env->n.p; x.aux = env->aux.p; x.acc = env->acc.p;
+            x.status = P.status.p; x.ep_count = P.ep_count.p; x.ep_sum = P.ep_sum.p;
+            if (c.log) { x.seg_cnt = P.log.seg_cnt.p; x.seg_step = P.log.seg_step.p; x.seg_ret = P.log.seg_ret.p; x.seg_len = k; }
+            x.seed_lo = (uint32_t)e->seed; x.seed_hi = (uint32_t)(e->seed >> 32);
+            x.nan_select = c.nan_select;
+            x.step0 = e->step_ctr + (unsigned long long)t; x.t_call = t;
+            x.step_off = P.off_any ? P.step_off.p : nullptr;
+            return own(l, tag);
+        };
+        return e->dtype == QE_F32 ? go(float{}) : go(double{});
+    });
+    if (v < 0) return qe_fail(QE_ERR_INVALID, "unknown env kind %d", (int)env->p.kind);
+    c.variant = v;
+    ++c.launches;
+    HIP_TRY(hipGetLastError());
+    if (c.log)
+        if (int rc = log_launch(e, k, c.L, c.launches)) return rc;
+    return QE_OK;
+}
+
+// The exit of a call: stops the clock and copies back (`own_copies` enqueues the caller's beside the common ones); then
+// `settle(env_steps)` advances the draw counters and does what else the caller derives per run; then the log in
+// (run, episode) order, the statistics, and the refusal that names the runs without a selectable action.  Returns the
+// episodes ended.
+template <class Copies, class Settle>
+int64_t call_end(PopCall& c, qe_rollout_stats* stats, int64_t* ep_count, float* ep_sum, uint32_t* status, Copies own_copies,
+                 Settle settle) {
+    qe_engine* e = c.e;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
+    HIP_TRY(hipEventRecord(P.ev1, e->stream));
+    std::vector<long long> counts(m);
+    c.st.resize(m);
+    HIP_TRY(hipMemcpyAsync(counts.data(), P.ep_count.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(c.st.data(), P.status.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    if (ep_sum) HIP_TRY(hipMemcpyAsync(ep_sum, P.ep_sum.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = own_copies()) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    long long total = 0, env_steps = 0;
+    if (int rc = settle(env_steps)) return rc;
+    for (size_t r = 0; r < m; ++r) {
+        if (ep_count) ep_count[r] = counts[r];
+        total += counts[r];
+    }
+    if (status) memcpy(status, c.st.data(), m * sizeof(uint32_t));
+    if (c.log) log_finish(P.log, m, c.L, counts);
+    if (stats) {
+        float ms = 0.0f;
+        if (c.launches) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
+        stats->kernel_ms = ms; stats->launches = c.launches; stats->episodes = total;
+        stats->dominant_ms = ms; stats->dominant_launches = c.launches; stats->dominant_env_steps = env_steps;
+        stats->kernel_variant = c.variant;
+    }
+    if (int rc = fail_empty(c.st)) return rc;
+    return total;
 }
 
 }  // namespace
@@ -278,29 +414,23 @@ int qe_create_population(qe_engine** out, int64_t runs, int64_t S, int32_t A, ui
     // (the touch counters serve the paths that order agents sharing a row: not this one)
     (void)hipFree(e->stamps);
     e->stamps = nullptr;
-    e->pop.runs = runs;
-    e->pop.S = S;
+    PopState& P = e->pop;
+    P.runs = runs;
+    P.S = S;
     const size_t m = (size_t)runs;
-    hipError_t err = e->pop.eps.ensure(m);
-    if (err == hipSuccess) err = e->pop.lr.ensure(m);
-    if (err == hipSuccess) err = e->pop.gamma.ensure(m);
-    if (err == hipSuccess) err = e->pop.status.ensure(m);
-    if (err == hipSuccess) err = e->pop.ep_count.ensure(m);
-    if (err == hipSuccess) err = e->pop.ep_sum.ensure(m);
-    if (err == hipSuccess) err = hipMemsetAsync(e->pop.eps.p, 0, m * sizeof(RunSched), e->stream);  // constant 0
-    if (err == hipSuccess) err = hipMemsetAsync(e->pop.lr.p, 0, m * sizeof(RunSched), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(e->pop.gamma.p, 0, m * sizeof(double), e->stream);
-    if (err == hipSuccess) err = hipEventCreate(&e->pop.ev0);
-    if (err == hipSuccess) err = hipEventCreate(&e->pop.ev1);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (err != hipSuccess) {
-        const int code = qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "population allocation failed: %s",
-                                 hipGetErrorString(err));
-        qe_destroy(e);
-        return code;
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t step) { return (err = step) == hipSuccess; };
+    if (ok(P.eps.ensure(m)) && ok(P.lr.ensure(m)) && ok(P.gamma.ensure(m)) && ok(P.status.ensure(m)) && ok(P.ep_count.ensure(m)) &&
+        ok(P.ep_sum.ensure(m)) && ok(hipMemsetAsync(P.eps.p, 0, m * sizeof(RunSched), e->stream)) &&  // constant 0
+        ok(hipMemsetAsync(P.lr.p, 0, m * sizeof(RunSched), e->stream)) && ok(hipMemsetAsync(P.gamma.p, 0, m * sizeof(double), e->stream)) &&
+        ok(hipEventCreate(&P.ev0)) && ok(hipEventCreate(&P.ev1)) && ok(hipStreamSynchronize(e->stream))) {
+        *out = e;
+        return QE_OK;
     }
-    *out = e;
-    return QE_OK;
+    const int code = qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "population allocation failed: %s",
+                             hipGetErrorString(err));
+    qe_destroy(e);
+    return code;
 }
 
 int64_t qe_population_runs(qe_engine* e) { return e ? e->pop.runs : 0; }
@@ -309,8 +439,8 @@ int qe_population_configure(qe_engine* e, const qe_run_schedule* eps, const qe_r
     if (int rc = need_population(e)) return rc;
     static_assert(sizeof(qe_run_schedule) == sizeof(RunSched), "qe_run_schedule and RunSched differ");
     const size_t m = (size_t)e->pop.runs;
-    if (gamma && e->pop.trace_k)  // (the kernel multiplies the traces by T(gamma * lambda))
-        if (int rc = check_trace_decay(e, gamma, e->pop.h_lambda.data())) return rc;
+    if (gamma && e->pop.trace.k)  // (the kernel multiplies the traces by T(gamma * lambda))
+        if (int rc = check_trace_decay(e, gamma, e->pop.trace.h_lambda.data())) return rc;
     for (const qe_run_schedule* d : {eps, lr})
         for (size_t r = 0; d && r < m; ++r)
             if (d[r].kind < QE_SCHED_CONSTANT || d[r].kind > QE_SCHED_EXPONENTIAL)
@@ -340,217 +470,96 @@ int qe_population_schedules(qe_engine* e, double* eps_values, double* lr_values)
 int64_t qe_population_rollout(qe_engine* e, qe_env* env, int64_t steps, int32_t mode, int32_t log, qe_rollout_stats* stats,
                               int64_t* ep_count, float* ep_sum, int32_t* obs, uint32_t* aux, float* agent_rewards,
                               uint32_t* status) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    P.log_step.clear();
-    P.log_ret.clear();
-    if (!env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
-    if (steps < 0) return qe_fail(QE_ERR_INVALID, "steps must be >= 0");
+    if (int rc = call_check(e, env, steps, stats)) return rc;
     if (mode != QE_LEARN_ITER && mode != QE_LEARN_VEC) return qe_fail(QE_ERR_INVALID, "bad learn mode");
-    if (e->ld > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions");
-    HIP_TRY(hipSetDevice(e->device));
-    const int64_t M = P.runs;
-    const size_t m = (size_t)M;
-    const long long per_launch = launch_len(M, steps, log != 0, P.planning);
-    if (log)
-        if (int rc = log_reserve(P, m, per_launch)) return rc;
-    env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
-    HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
-    HIP_TRY(hipMemsetAsync(P.ep_sum.p, 0, m * sizeof(float), e->stream));
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs;
     // One agent per run: the reference's dispatcher picks the list variants of the selection (they step over a NaN)
     // except for masked rows of more than 10 actions (q_learning_optimal.py:700, :713; see rollout_ctx)
     const bool masked = env->p.masked != 0 || env->p.kind == QE_ENV_TICTACTOE;
-    const int nan_select = masked && e->A > 10 ? 1 : 0;
-    const EnvCtx ev = make_envctx(e, env);
-    if (P.rule == QE_RULE_SARSA)
-        if (int rc = pending_reserve(e)) return rc;
-    CallLog L;
-    int64_t launches = 0, variant = P.table_b ? QE_VARIANT_RUNS_DOUBLE : QE_VARIANT_RUNS;
-    HIP_TRY(hipEventRecord(P.ev0, e->stream));
-    for (long long t = 0; t < steps; t += per_launch) {
-        const long long k = std::min<long long>(per_launch, steps - t);
-        const int64_t v = by_env(env->p.kind, [&](auto tag) -> int64_t {
-            using Env = decltype(tag);
-            auto go = [&](auto tt) -> int64_t {
-                using T = decltype(tt);
-                RunsCtx<T> c{};
-                c.q = (T*)e->q; c.S = P.S; c.M = M;
-                c.obs = env->n.p; c.aux = env->aux.p; c.acc = env->acc.p;
-                c.eps = P.eps.p; c.lr = P.lr.p; c.gamma = P.gamma.p; c.status = P.status.p;
-                c.ep_count = P.ep_count.p; c.ep_sum = P.ep_sum.p;
-                if (log) { c.seg_cnt = P.seg_cnt.p; c.seg_step = P.seg_step.p; c.seg_ret = P.seg_ret.p; c.seg_len = k; }
-                c.seed_lo = (uint32_t)e->seed; c.seed_hi = (uint32_t)(e->seed >> 32);
-                c.mode = mode; c.nan_select = nan_select;
-                c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
-                c.step_off = P.off_any ? P.step_off.p : nullptr;
-                if (P.table_b) return launch_double_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, (T*)P.table_b);
-                if (P.planning) {
-                    const DynaModel w{P.planning, P.dyna_entry.p, P.dyna_visited.p, P.dyna_count.p, P.S * (int64_t)e->A};
-                    return launch_dyna_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, w);
-                }
-                if (P.trace_k) {
-                    const TraceSlots<T> w{P.trace_k, P.trace_kind, P.trace_s.p, P.trace_a.p, (T*)P.trace_e.p, P.trace_lambda.p};
-                    return launch_trace_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
-                }
-                if (P.n_step > 1) {
-                    const NStepWin w{P.n_step, P.win_len.p, P.win_s.p, P.win_a.p, P.win_r.p};
-                    return launch_nstep_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p, w);
-                }
-                if (P.rule != QE_RULE_Q_LEARNING)
-                    return launch_runs_td<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, P.rule, P.pending.p);
-                return launch_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k);
-            };
-            return e->dtype == QE_F32 ? go(float{}) : go(double{});
+    PopCall c{e, env, steps, log != 0, masked && e->A > 10 ? 1 : 0, P.table_b ? QE_VARIANT_RUNS_DOUBLE : QE_VARIANT_RUNS};
+    if (int rc = call_begin(c, P.dyna.planning, [&] { return P.rule == QE_RULE_SARSA ? pending_reserve(e) : QE_OK; })) return rc;
+    for (long long t = 0; t < steps; t += c.per_launch)
+        if (int rc = call_launch(c, t, std::min<long long>(c.per_launch, steps - t), [&](auto& l, auto tag) {
+                l.c.eps = P.eps.p; l.c.lr = P.lr.p; l.c.gamma = P.gamma.p; l.c.mode = mode;
+                return launch_training<std::decay_t<decltype(*l.c.q)>, decltype(tag)>(e, l);
+            }))
+            return rc;
+    return call_end(
+        c, stats, ep_count, ep_sum, status,
+        [&]() -> int {
+            if (obs) HIP_TRY(hipMemcpyAsync(obs, env->n.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+            if (aux) HIP_TRY(hipMemcpyAsync(aux, env->aux.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+            if (agent_rewards) HIP_TRY(hipMemcpyAsync(agent_rewards, env->acc.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+            return QE_OK;
+        },
+        [&](long long& env_steps) {
+            e->step_ctr += (uint64_t)steps;
+            env_steps = steps * P.runs;
+            return QE_OK;
         });
-        if (v < 0) return qe_fail(QE_ERR_INVALID, "unknown env kind %d", (int)env->p.kind);
-        variant = v;
-        ++launches;
-        HIP_TRY(hipGetLastError());
-        if (log)
-            if (int rc = log_launch(e, k, L, launches)) return rc;
-    }
-    HIP_TRY(hipEventRecord(P.ev1, e->stream));
-    e->step_ctr += (uint64_t)steps;
-    std::vector<long long> counts(m);
-    std::vector<uint32_t> st(m);
-    HIP_TRY(hipMemcpyAsync(counts.data(), P.ep_count.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), P.status.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    if (ep_sum) HIP_TRY(hipMemcpyAsync(ep_sum, P.ep_sum.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    if (obs) HIP_TRY(hipMemcpyAsync(obs, env->n.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (aux) HIP_TRY(hipMemcpyAsync(aux, env->aux.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    if (agent_rewards) HIP_TRY(hipMemcpyAsync(agent_rewards, env->acc.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipGetLastError());
-    long long total = 0;
-    for (size_t r = 0; r < m; ++r) {
-        if (ep_count) ep_count[r] = counts[r];
-        total += counts[r];
-    }
-    if (status) memcpy(status, st.data(), m * sizeof(uint32_t));
-    if (log) log_finish(P, L, counts);
-    if (stats) {
-        float ms = 0.0f;
-        if (steps > 0) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
-        stats->kernel_ms = ms; stats->launches = launches; stats->episodes = total;
-        stats->dominant_ms = ms; stats->dominant_launches = launches; stats->dominant_env_steps = steps * M;
-        stats->kernel_variant = variant;
-    }
-    if (int rc = fail_empty(st)) return rc;
-    return total;
 }
 
 int64_t qe_population_evaluate(qe_engine* e, qe_env* env, int64_t steps, int64_t episodes, int32_t log, qe_rollout_stats* stats,
                                int64_t* ep_count, float* ep_sum, int64_t* used, uint32_t* status) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    P.log_step.clear();
-    P.log_ret.clear();
-    if (!env || env->e != e) return qe_fail(QE_ERR_INVALID, "engine/env mismatch");
-    if (steps < 0) return qe_fail(QE_ERR_INVALID, "steps must be >= 0");
+    if (int rc = call_check(e, env, steps, stats)) return rc;
     if (episodes < 0) return qe_fail(QE_ERR_INVALID, "episodes must be >= 0");
-    if (e->ld > 64) return qe_fail(QE_ERR_UNSUPPORTED, "a population holds rows of at most 64 actions");
-    HIP_TRY(hipSetDevice(e->device));
-    const int64_t M = P.runs;
-    const size_t m = (size_t)M;
-    const long long per_launch = launch_len(M, steps, log != 0);
-    if (log)
-        if (int rc = log_reserve(P, m, per_launch)) return rc;
-    if (episodes) {
-        HIP_TRY(P.used.ensure(m)); HIP_TRY(P.done.ensure(m)); HIP_TRY(P.h_done.ensure(m));
-        HIP_TRY(hipMemsetAsync(P.used.p, 0, m * sizeof(long long), e->stream));
-        HIP_TRY(hipMemsetAsync(P.done.p, 0, m, e->stream));
-    }
-    env->mirror_obs = nullptr; env->mirror_aux = nullptr; env->mirror_acc = nullptr;  // the device state moves on
-    HIP_TRY(hipMemsetAsync(P.status.p, 0, m * sizeof(uint32_t), e->stream));
-    HIP_TRY(hipMemsetAsync(P.ep_count.p, 0, m * sizeof(long long), e->stream));
-    HIP_TRY(hipMemsetAsync(P.ep_sum.p, 0, m * sizeof(float), e->stream));
+    PopState& P = e->pop;
+    PopState::EpisodeMode& G = P.epi;
+    const size_t m = (size_t)P.runs;
     // The standalone evaluation's rule (rollout_ctx): deterministic selection takes the list variants, which step over a
     // NaN, for rows of at most 10 actions (q_learning_optimal.py:673), masked or not
-    const int nan_select = e->A > 10 ? 1 : 0;
-    const EnvCtx ev = make_envctx(e, env);
-    CallLog L;
-    int64_t launches = 0, variant = P.table_b ? QE_VARIANT_RUNS_DOUBLE_EVAL : QE_VARIANT_RUNS_EVAL;
+    PopCall c{e, env, steps, log != 0, e->A > 10 ? 1 : 0, P.table_b ? QE_VARIANT_RUNS_DOUBLE_EVAL : QE_VARIANT_RUNS_EVAL};
+    if (int rc = call_begin(c, 0, [&]() -> int {
+            if (!episodes) return QE_OK;
+            HIP_TRY(G.used.ensure(m)); HIP_TRY(G.done.ensure(m)); HIP_TRY(G.h_done.ensure(m));
+            HIP_TRY(hipMemsetAsync(G.used.p, 0, m * sizeof(long long), e->stream));
+            HIP_TRY(hipMemsetAsync(G.done.p, 0, m, e->stream));
+            return QE_OK;
+        }))
+        return rc;
     bool all_done = false;
-    HIP_TRY(hipEventRecord(P.ev0, e->stream));
-    for (long long t = 0; t < steps && !all_done; t += per_launch) {
-        const long long k = std::min<long long>(per_launch, steps - t);
-        const int64_t v = by_env(env->p.kind, [&](auto tag) -> int64_t {
-            using Env = decltype(tag);
-            auto go = [&](auto tt) -> int64_t {
-                using T = decltype(tt);
-                RunsCtx<T> c{};
-                c.q = (T*)e->q; c.S = P.S; c.M = M;
-                c.obs = env->n.p; c.aux = env->aux.p; c.acc = env->acc.p;
-                c.status = P.status.p; c.ep_count = P.ep_count.p; c.ep_sum = P.ep_sum.p;
-                if (log) { c.seg_cnt = P.seg_cnt.p; c.seg_step = P.seg_step.p; c.seg_ret = P.seg_ret.p; c.seg_len = k; }
-                c.seed_lo = (uint32_t)e->seed; c.seed_hi = (uint32_t)(e->seed >> 32);
-                c.nan_select = nan_select;
-                c.step0 = e->step_ctr + (unsigned long long)t; c.t_call = t;
-                c.step_off = P.off_any ? P.step_off.p : nullptr;
-                if (P.table_b)
-                    return launch_double_evaluate<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, episodes,
-                                                          episodes ? P.used.p : nullptr, episodes ? P.done.p : nullptr,
-                                                          (const T*)P.table_b);
-                return launch_evaluate_runs<T, Env>(e->stream, c, ev, e->ld, env->p.masked != 0, k, episodes,
-                                                    episodes ? P.used.p : nullptr, episodes ? P.done.p : nullptr);
-            };
-            return e->dtype == QE_F32 ? go(float{}) : go(double{});
-        });
-        if (v < 0) return qe_fail(QE_ERR_INVALID, "unknown env kind %d", (int)env->p.kind);
-        variant = v;
-        ++launches;
-        HIP_TRY(hipGetLastError());
-        if (log)
-            if (int rc = log_launch(e, k, L, launches)) return rc;
+    for (long long t = 0; t < steps && !all_done; t += c.per_launch) {
+        if (int rc = call_launch(c, t, std::min<long long>(c.per_launch, steps - t), [&](auto& l, auto tag) {
+                using T = std::decay_t<decltype(*l.c.q)>;
+                long long* const took = episodes ? G.used.p : nullptr;
+                uint8_t* const done = episodes ? G.done.p : nullptr;
+                if (P.table_b) return launch_double_evaluate<T, decltype(tag)>(l, episodes, took, done, (const T*)P.table_b);
+                return launch_evaluate_runs<T, decltype(tag)>(l, episodes, took, done);
+            }))
+            return rc;
         if (episodes) {  // no further launch once every run has its episodes
-            HIP_TRY(hipMemcpyAsync(P.h_done.p, P.done.p, m, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(G.h_done.p, G.done.p, m, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
-            all_done = std::all_of(P.h_done.p, P.h_done.p + m, [](uint8_t d) { return d != 0; });
+            all_done = std::all_of(G.h_done.p, G.h_done.p + m, [](uint8_t d) { return d != 0; });
         }
     }
-    HIP_TRY(hipEventRecord(P.ev1, e->stream));
-    std::vector<long long> counts(m), took(m, steps);
-    std::vector<uint32_t> st(m);
-    HIP_TRY(hipMemcpyAsync(counts.data(), P.ep_count.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), P.status.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    if (ep_sum) HIP_TRY(hipMemcpyAsync(ep_sum, P.ep_sum.p, m * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    if (episodes) {
-        HIP_TRY(hipMemcpyAsync(took.data(), P.used.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(P.h_done.p, P.done.p, m, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipGetLastError());
-    // every run's draw counter moves on by the steps it took (the standalone evaluate_episodes: start + used)
-    if (episodes) {
-        std::vector<uint64_t> ctr(m);
-        if (int rc = get_counters(e, ctr.data())) return rc;
-        for (size_t r = 0; r < m; ++r) ctr[r] += (uint64_t)took[r];
-        if (int rc = set_counters(e, ctr.data())) return rc;
-    } else {
-        e->step_ctr += (uint64_t)steps;
-    }
-    long long total = 0, env_steps = 0;
-    for (size_t r = 0; r < m; ++r) {
-        if (episodes && !P.h_done.p[r]) st[r] |= 2u;  // stopped by the bound `steps`
-        if (ep_count) ep_count[r] = counts[r];
-        if (used) used[r] = took[r];
-        total += counts[r];
-        env_steps += took[r];
-    }
-    if (status) memcpy(status, st.data(), m * sizeof(uint32_t));
-    if (log) log_finish(P, L, counts);
-    if (stats) {
-        float ms = 0.0f;
-        if (launches) HIP_TRY(hipEventElapsedTime(&ms, P.ev0, P.ev1));
-        stats->kernel_ms = ms; stats->launches = launches; stats->episodes = total;
-        stats->dominant_ms = ms; stats->dominant_launches = launches; stats->dominant_env_steps = env_steps;
-        stats->kernel_variant = variant;
-    }
-    if (int rc = fail_empty(st)) return rc;
-    return total;
+    std::vector<long long> took(m, steps);
+    return call_end(
+        c, stats, ep_count, ep_sum, status,
+        [&]() -> int {
+            if (!episodes) return QE_OK;
+            HIP_TRY(hipMemcpyAsync(took.data(), G.used.p, m * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipMemcpyAsync(G.h_done.p, G.done.p, m, hipMemcpyDeviceToHost, e->stream));
+            return QE_OK;
+        },
+        [&](long long& env_steps) -> int {
+            // every run's draw counter moves on by the steps it took (the standalone evaluate_episodes: start + used)
+            if (episodes) {
+                std::vector<uint64_t> ctr(m);
+                if (int rc = get_counters(e, ctr.data())) return rc;
+                for (size_t r = 0; r < m; ++r) ctr[r] += (uint64_t)took[r];
+                if (int rc = set_counters(e, ctr.data())) return rc;
+            } else {
+                e->step_ctr += (uint64_t)steps;
+            }
+            for (size_t r = 0; r < m; ++r) {
+                if (episodes && !G.h_done.p[r]) c.st[r] |= 2u;  // stopped by the bound `steps`
+                if (used) used[r] = took[r];
+                env_steps += took[r];
+            }
+            return QE_OK;
+        });
 }
 
 int qe_population_step_counters(qe_engine* e, uint64_t* out) {
@@ -573,17 +582,17 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
         return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
     if (e->pop.table_b && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (qe_population_set_double)");
-    if (e->pop.n_step > 1 && rule == QE_RULE_Q_LEARNING)
+    if (e->pop.win.n > 1 && rule == QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (importance sampling and "
                        "tree backup are not built); the n-step rules are SARSA and Expected SARSA",
-                       e->pop.n_step);
-    if (e->pop.planning && rule != QE_RULE_Q_LEARNING)
+                       e->pop.win.n);
+    if (e->pop.dyna.planning && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "planning is on (%d updates per step): Dyna-Q replays remembered transitions through Q-learning's update; "
                        "planning for the on-policy rules is not built (qe_population_set_planning)",
-                       e->pop.planning);
-    if (e->pop.trace_k && rule == QE_RULE_EXPECTED_SARSA)
+                       e->pop.dyna.planning);
+    if (e->pop.trace.k && rule == QE_RULE_EXPECTED_SARSA)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "eligibility traces are on: the trace form of Expected SARSA needs policy-probability weighting, which "
                        "is not built; the trace rules are SARSA and Q-learning (qe_population_set_traces)");
@@ -599,11 +608,11 @@ int qe_population_update_rule(qe_engine* e) {
 int qe_population_set_double(qe_engine* e, int32_t on) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    if (on && P.n_step > 1)
-        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.n_step);
-    if (on && P.trace_k)
+    if (on && P.win.n > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.win.n);
+    if (on && P.trace.k)
         return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces are on: the double estimator has no trace form (qe_population_set_traces)");
-    if (on && P.planning)
+    if (on && P.dyna.planning)
         return qe_fail(QE_ERR_UNSUPPORTED, "planning is on: Dyna-Q plans on one table (qe_population_set_planning)");
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (update rule %d)", P.rule);
@@ -699,48 +708,45 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
                        (int)n);
     if (n > 1 && P.table_b)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
-    if (n > 1 && P.planning)
+    if (n > 1 && P.dyna.planning)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)", (int)n);
-    if (n > 1 && P.trace_k)
+    if (n > 1 && P.trace.k)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
-    if (n == P.n_step) return QE_OK;
+    if (n == P.win.n) return QE_OK;
     HIP_TRY(hipSetDevice(e->device));
     if (n > 1) {
         if (int rc = window_reserve(e, n)) return rc;
     } else {
         HIP_TRY(hipStreamSynchronize(e->stream));
-        P.win_len.release(); P.win_s.release(); P.win_a.release(); P.win_r.release();
+        P.win.release();
     }
-    P.n_step = n;
+    P.win.n = n;
     return QE_OK;
 }
 
 int qe_population_n_step(qe_engine* e) {
     if (int rc = need_population(e)) return rc;
-    return e->pop.n_step;
+    return e->pop.win.n;
 }
 
 int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.n_step - 1);
+    const size_t m = (size_t)P.runs, w = (size_t)(P.win.n - 1);
     if (!w) return QE_OK;  // a one-step rule has no window: nothing to write
     if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
     HIP_TRY(hipSetDevice(e->device));
     std::vector<int32_t> hs(m * w), ha(m * w);
     std::vector<float> hr(m * w);
-    HIP_TRY(hipMemcpyAsync(len, P.win_len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hs.data(), P.win_s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(ha.data(), P.win_a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hr.data(), P.win_r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(len, P.win.len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), P.win.s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), P.win.a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), P.win.r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    for (size_t r = 0; r < m; ++r)  // [slot][run] -> [run][slot]; slots past the length hold 0
-        for (size_t i = 0; i < w; ++i) {
-            const bool used = (int32_t)i < len[r];
-            if (states) states[r * w + i] = used ? hs[i * m + r] : 0;
-            if (actions) actions[r * w + i] = used ? ha[i * m + r] : 0;
-            if (rewards) rewards[r * w + i] = used ? hr[i * m + r] : 0.0f;
-        }
+    auto used = [&](size_t r, size_t i) { return (int32_t)i < len[r]; };  // slots past the length hold 0
+    slots_to_abi(hs.data(), states, m, w, used);
+    slots_to_abi(ha.data(), actions, m, w, used);
+    slots_to_abi(hr.data(), rewards, m, w, used);
     return QE_OK;
 }
 
@@ -748,7 +754,7 @@ int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* st
                              const float* rewards) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.n_step - 1);
+    const size_t m = (size_t)P.runs, w = (size_t)(P.win.n - 1);
     if (!w) {
         for (size_t r = 0; len && r < m; ++r)
             if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with n_step = 1", (long long)r, (int)len[r]);
@@ -756,13 +762,11 @@ int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* st
     }
     HIP_TRY(hipSetDevice(e->device));
     if (!len) {  // every window empty
-        HIP_TRY(hipMemsetAsync(P.win_len.p, 0, m * sizeof(int32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(P.win.len.p, 0, m * sizeof(int32_t), e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         return QE_OK;
     }
     if (!states || !actions || !rewards) return qe_fail(QE_ERR_INVALID, "states, actions or rewards is NULL");
-    std::vector<int32_t> hs(m * w, 0), ha(m * w, 0);
-    std::vector<float> hr(m * w, 0.0f);
     for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
         if (len[r] < 0 || len[r] > (int32_t)w)
             return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
@@ -772,13 +776,18 @@ int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* st
                 return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)P.S);
             if (a < 0 || a >= e->A)
                 return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
-            hs[i * m + r] = s; ha[i * m + r] = a; hr[i * m + r] = rewards[r * w + i];
         }
     }
-    HIP_TRY(hipMemcpyAsync(P.win_len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win_s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win_a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win_r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    std::vector<int32_t> hs(m * w), ha(m * w);
+    std::vector<float> hr(m * w);
+    auto used = [&](size_t r, size_t i) { return i < (size_t)len[r]; };
+    slots_to_device(states, hs.data(), m, w, used);
+    slots_to_device(actions, ha.data(), m, w, used);
+    slots_to_device(rewards, hr.data(), m, w, used);
+    HIP_TRY(hipMemcpyAsync(P.win.len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win.s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win.a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.win.r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
@@ -788,12 +797,10 @@ int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double
     PopState& P = e->pop;
     const size_t m = (size_t)P.runs;
     if (!lambda) {  // off
-        if (!P.trace_k) return QE_OK;
+        if (!P.trace.k) return QE_OK;
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        P.trace_s.release(); P.trace_a.release(); P.trace_e.release(); P.trace_lambda.release();
-        P.h_lambda.clear();
-        P.trace_k = 0;
+        P.trace.release();
         return QE_OK;
     }
     if (K < 1 || K > TRACE_MAX) return qe_fail(QE_ERR_INVALID, "trace_length must be in 1 .. %d, got %d", TRACE_MAX, (int)K);
@@ -807,71 +814,66 @@ int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double
                        "eligibility traces with Expected SARSA: its trace form needs policy-probability weighting, which is not "
                        "built; the trace rules are SARSA and Q-learning");
     if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces: the double estimator has no trace form (qe_population_set_double)");
-    if (P.planning)
+    if (P.dyna.planning)
         return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)");
-    if (P.n_step > 1)
-        return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces with n_step = %d: one multi-step method at a time (qe_population_set_n_step)", P.n_step);
+    if (P.win.n > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "eligibility traces with n_step = %d: one multi-step method at a time (qe_population_set_n_step)", P.win.n);
     HIP_TRY(hipSetDevice(e->device));
     std::vector<double> gamma(m);
     HIP_TRY(hipMemcpyAsync(gamma.data(), P.gamma.p, m * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (int rc = check_trace_decay(e, gamma.data(), lambda)) return rc;
     const size_t cells = m * (size_t)K;
-    HIP_TRY(P.trace_s.ensure(cells)); HIP_TRY(P.trace_a.ensure(cells)); HIP_TRY(P.trace_e.ensure(cells)); HIP_TRY(P.trace_lambda.ensure(m));
-    HIP_TRY(hipMemcpyAsync(P.trace_lambda.p, lambda, m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    PopState::Traces& X = P.trace;
+    HIP_TRY(X.s.ensure(cells)); HIP_TRY(X.a.ensure(cells)); HIP_TRY(X.e.ensure(cells)); HIP_TRY(X.lambda.ensure(m));
+    HIP_TRY(hipMemcpyAsync(X.lambda.p, lambda, m * sizeof(double), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    P.h_lambda.assign(lambda, lambda + m);
-    P.trace_k = K;
-    P.trace_kind = kind;
+    X.h_lambda.assign(lambda, lambda + m);
+    X.k = K;
+    X.kind = kind;
     return traces_clear(e);
 }
 
 int qe_population_trace_config(qe_engine* e, int32_t* K, int32_t* kind, double* lambda) {
     if (int rc = need_population(e)) return rc;
-    const PopState& P = e->pop;
-    if (K) *K = P.trace_k;
-    if (kind) *kind = P.trace_k ? P.trace_kind : 0;
-    if (lambda && P.trace_k) std::copy(P.h_lambda.begin(), P.h_lambda.end(), lambda);
-    return P.trace_k ? 1 : 0;
+    const PopState::Traces& X = e->pop.trace;
+    if (K) *K = X.k;
+    if (kind) *kind = X.k ? X.kind : 0;
+    if (lambda && X.k) std::copy(X.h_lambda.begin(), X.h_lambda.end(), lambda);
+    return X.k ? 1 : 0;
 }
 
 int qe_population_traces(qe_engine* e, int32_t* states, int32_t* actions, double* values) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    if (!P.trace_k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
-    const size_t m = (size_t)P.runs, k = (size_t)P.trace_k;
+    if (!P.trace.k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
+    const size_t m = (size_t)P.runs, k = (size_t)P.trace.k;
     const bool f32 = e->dtype == QE_F32;
     HIP_TRY(hipSetDevice(e->device));
     std::vector<int32_t> hs(m * k), ha(m * k);
     std::vector<double> he(m * k);
-    HIP_TRY(hipMemcpyAsync(hs.data(), P.trace_s.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(ha.data(), P.trace_a.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(he.data(), P.trace_e.p, m * k * e->esize(), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), P.trace.s.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), P.trace.a.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(he.data(), P.trace.e.p, m * k * e->esize(), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const float* const he32 = reinterpret_cast<const float*>(he.data());
-    for (size_t r = 0; r < m; ++r)  // [slot][run] -> [run][slot]; free slots read (0, 0, 0.0)
-        for (size_t i = 0; i < k; ++i) {
-            const double v = f32 ? (double)he32[i * m + r] : he[i * m + r];
-            const bool live = v != 0.0;
-            if (states) states[r * k + i] = live ? hs[i * m + r] : 0;
-            if (actions) actions[r * k + i] = live ? ha[i * m + r] : 0;
-            if (values) values[r * k + i] = live ? v : 0.0;
-        }
+    auto live = [&](size_t r, size_t i) { return (f32 ? (double)he32[i * m + r] : he[i * m + r]) != 0.0; };  // free slots read (0, 0, 0.0)
+    slots_to_abi(hs.data(), states, m, k, live);
+    slots_to_abi(ha.data(), actions, m, k, live);
+    if (f32) slots_to_abi(he32, values, m, k, live);
+    else slots_to_abi(he.data(), values, m, k, live);
     return QE_OK;
 }
 
 int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int32_t* actions, const double* values) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    if (!P.trace_k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
+    if (!P.trace.k) return qe_fail(QE_ERR_INVALID, "eligibility traces are off (qe_population_set_traces)");
     HIP_TRY(hipSetDevice(e->device));
     if (!states && !actions && !values) return traces_clear(e);
     if (!states || !actions || !values) return qe_fail(QE_ERR_INVALID, "states, actions or values is NULL");
-    const size_t m = (size_t)P.runs, k = (size_t)P.trace_k;
+    const size_t m = (size_t)P.runs, k = (size_t)P.trace.k;
     const bool f32 = e->dtype == QE_F32;
-    std::vector<int32_t> hs(m * k, 0), ha(m * k, 0);
-    std::vector<double> he(m * k, 0.0);
-    float* const he32 = reinterpret_cast<float*>(he.data());
     for (size_t r = 0; r < m; ++r)  // (the kernel indexes the run's table with the live slots)
         for (size_t i = 0; i < k; ++i) {
             const double v = values[r * k + i];
@@ -890,13 +892,17 @@ int qe_population_set_trace_state(qe_engine* e, const int32_t* states, const int
                 if (values[r * k + j] != 0.0 && states[r * k + j] == s && actions[r * k + j] == a)
                     return qe_fail(QE_ERR_INVALID, "trace slots %d and %d of run %lld name the same cell (%d, %d)", (int)j, (int)i,
                                    (long long)r, (int)s, (int)a);
-            hs[i * m + r] = s; ha[i * m + r] = a;
-            if (f32) he32[i * m + r] = (float)v;
-            else he[i * m + r] = v;
         }
-    HIP_TRY(hipMemcpyAsync(P.trace_s.p, hs.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.trace_a.p, ha.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.trace_e.p, he.data(), m * k * e->esize(), hipMemcpyHostToDevice, e->stream));
+    std::vector<int32_t> hs(m * k), ha(m * k);
+    std::vector<double> he(m * k);
+    auto live = [&](size_t r, size_t i) { return values[r * k + i] != 0.0; };
+    slots_to_device(states, hs.data(), m, k, live);
+    slots_to_device(actions, ha.data(), m, k, live);
+    if (f32) slots_to_device(values, reinterpret_cast<float*>(he.data()), m, k, live);
+    else slots_to_device(values, he.data(), m, k, live);
+    HIP_TRY(hipMemcpyAsync(P.trace.s.p, hs.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.trace.a.p, ha.data(), m * k * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.trace.e.p, he.data(), m * k * e->esize(), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
@@ -906,11 +912,10 @@ int qe_population_set_planning(qe_engine* e, int32_t n) {
     PopState& P = e->pop;
     if (n < 0 || n > DYNA_MAX) return qe_fail(QE_ERR_INVALID, "planning_steps must be in 0 .. %d, got %d", DYNA_MAX, (int)n);
     if (n == 0) {  // off: the model is forgotten
-        if (!P.planning) return QE_OK;
+        if (!P.dyna.planning) return QE_OK;
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipStreamSynchronize(e->stream));
-        P.dyna_entry.release(); P.dyna_visited.release(); P.dyna_count.release();
-        P.planning = 0;
+        P.dyna.release();
         return QE_OK;
     }
     if (P.rule != QE_RULE_Q_LEARNING)
@@ -919,49 +924,49 @@ int qe_population_set_planning(qe_engine* e, int32_t n) {
                        "for the on-policy rules is not built",
                        P.rule);
     if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "planning: Dyna-Q plans on one table, the double estimator has two (qe_population_set_double)");
-    if (P.n_step > 1)
-        return qe_fail(QE_ERR_UNSUPPORTED, "planning with n_step = %d: Dyna-Q is a one-step method (qe_population_set_n_step)", P.n_step);
-    if (P.trace_k) return qe_fail(QE_ERR_UNSUPPORTED, "planning with eligibility traces: Dyna-Q is a one-step method (qe_population_set_traces)");
+    if (P.win.n > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "planning with n_step = %d: Dyna-Q is a one-step method (qe_population_set_n_step)", P.win.n);
+    if (P.trace.k) return qe_fail(QE_ERR_UNSUPPORTED, "planning with eligibility traces: Dyna-Q is a one-step method (qe_population_set_traces)");
     // (the list and the kernel name a cell by its offset in the run's table, an int32; ld >= A)
     if ((double)P.S * (double)e->ld >= 2147483648.0)
         return qe_fail(QE_ERR_UNSUPPORTED, "planning: a run's table must hold fewer than 2^31 cells (state_size * row stride = %lld * %d)",
                        (long long)P.S, (int)e->ld);
-    if (P.planning) {  // already on: the model is knowledge and stays
-        P.planning = n;
+    if (P.dyna.planning) {  // already on: the model is knowledge and stays
+        P.dyna.planning = n;
         return QE_OK;
     }
     HIP_TRY(hipSetDevice(e->device));
     const size_t m = (size_t)P.runs;
-    hipError_t err = P.dyna_entry.ensure(m * (size_t)P.S * (size_t)e->ld);
-    if (err == hipSuccess) err = P.dyna_visited.ensure(m * (size_t)P.S * (size_t)e->A);
-    if (err == hipSuccess) err = P.dyna_count.ensure(m);
+    hipError_t err = P.dyna.entry.ensure(m * (size_t)P.S * (size_t)e->ld);
+    if (err == hipSuccess) err = P.dyna.visited.ensure(m * (size_t)P.S * (size_t)e->A);
+    if (err == hipSuccess) err = P.dyna.count.ensure(m);
     if (err != hipSuccess) {
         (void)hipGetLastError();
-        P.dyna_entry.release(); P.dyna_visited.release(); P.dyna_count.release();
+        P.dyna.release();
         return qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "planning: the model could not be allocated: %s",
                        hipGetErrorString(err));
     }
     if (int rc = model_clear(e)) return rc;
-    P.planning = n;
+    P.dyna.planning = n;
     return QE_OK;
 }
 
 int qe_population_planning(qe_engine* e) {
     if (int rc = need_population(e)) return rc;
-    return e->pop.planning;
+    return e->pop.dyna.planning;
 }
 
 int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint8_t* terminated, int32_t* visited, int32_t* count) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    if (!P.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
     const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
     HIP_TRY(hipSetDevice(e->device));
     std::vector<int32_t> hc(m);
-    HIP_TRY(hipMemcpyAsync(hc.data(), P.dyna_count.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hc.data(), P.dyna.count.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     if (next_states || rewards || terminated) {
         std::vector<uint2> he(m * S * ld);
-        HIP_TRY(hipMemcpyAsync(he.data(), P.dyna_entry.p, he.size() * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(he.data(), P.dyna.entry.p, he.size() * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         for (size_t r = 0; r < m; ++r)
             for (size_t s = 0; s < S; ++s)
@@ -979,7 +984,7 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
     }
     if (visited) {
         std::vector<int32_t> hv(m * S * A);
-        HIP_TRY(hipMemcpyAsync(hv.data(), P.dyna_visited.p, hv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(hv.data(), P.dyna.visited.p, hv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         for (size_t r = 0; r < m; ++r)  // table offsets s * ld + a -> cells s * A + a; -1 past the count
             for (size_t j = 0; j < S * A; ++j) {
@@ -996,7 +1001,7 @@ int qe_population_set_model(qe_engine* e, const int32_t* next_states, const floa
                             const int32_t* visited, const int32_t* count) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
-    if (!P.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
     HIP_TRY(hipSetDevice(e->device));
     if (!next_states && !rewards && !terminated && !visited && !count) return model_clear(e);
     if (!next_states || !rewards || !terminated || !visited || !count)
@@ -1037,19 +1042,19 @@ int qe_population_set_model(qe_engine* e, const int32_t* next_states, const floa
             hv[r * S * A + j] = (int32_t)((size_t)c / A * ld + (size_t)c % A);
         }
     }
-    HIP_TRY(hipMemcpyAsync(P.dyna_entry.p, he.data(), he.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.dyna_visited.p, hv.data(), hv.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.dyna_count.p, count, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.entry.p, he.data(), he.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.visited.p, hv.data(), hv.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.count.p, count, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return QE_OK;
 }
 
 int64_t qe_population_log(qe_engine* e, int64_t cap, int32_t* step, float* ret) {
     if (int rc = need_population(e)) return rc;
-    const int64_t n = (int64_t)e->pop.log_step.size();
+    const int64_t n = (int64_t)e->pop.log.step.size();
     for (int64_t k = 0; k < n && k < cap; ++k) {
-        if (step) step[k] = e->pop.log_step[(size_t)k];
-        if (ret) ret[k] = e->pop.log_ret[(size_t)k];
+        if (step) step[k] = e->pop.log.step[(size_t)k];
+        if (ret) ret[k] = e->pop.log.ret[(size_t)k];
     }
     return n;
 }

@@ -284,3 +284,143 @@ def test_an_environment_that_outlives_its_population_is_released_cleanly():
     env.close()    # ... then its environment
     algo = OptimalQLearningBase(3, 3, 0.9, seed=0, dtype=np.float32)  # (padded rows: qe_create checks its launch)
     assert np.array_equal(np.asarray(algo.q_table), np.zeros((3, 3), dtype=np.float32))
+
+
+# ---- host bookkeeping around the launches: refused calls, zero-step calls, a method switched off and on again -----------------
+TINY = (3, 4, 2)  # runs, states, actions
+METHODS = [({"update_rule": "sarsa"}, 6), ({"update_rule": "expected_sarsa", "n_step": 3}, 6),
+           ({"update_rule": "sarsa", "trace_decay": 0.5, "trace_length": 4}, 6), ({"planning_steps": 2}, 6), ({"double_q": True}, 9)]
+
+
+def _tiny(**kw):
+    _, envs, sch, QLearningPopulation, *_ = _product()
+    pop = QLearningPopulation(*TINY, 0.9, sch.ExponentialSchedule(0.5, 0.01, 0.99), sch.LinearSchedule(0.9, -0.001), seed=3,
+                              dtype=np.float32, **kw)
+    return pop, envs.HashTabularEnv(*TINY, seed=1, p_term_256=64)
+
+
+def _same_dict(a, b):
+    assert sorted(a) == sorted(b)
+    for key, value in b.items():
+        if isinstance(value, dict):
+            _same_dict(a[key], value)
+        else:
+            assert np.array_equal(a[key], value), key
+
+
+def _same_call(pop, res, want_pop, want):
+    """Two populations after a call each: tables, model, result and state dict are equal."""
+    assert np.array_equal(pop.q_tables, want_pop.q_tables)
+    if pop.double_q:
+        assert np.array_equal(pop.q_tables_b, want_pop.q_tables_b)
+    if pop.planning_steps:
+        _same_dict(pop.planning_model, want_pop.planning_model)
+    for field in ("mean_returns", "episode_counts", "returns", "offsets", "steps"):
+        assert np.array_equal(getattr(res, field), getattr(want, field), equal_nan=True), field
+    _same_dict(res.state_dict, want.state_dict)
+    assert pop.last_stats["kernel_variant"] == want_pop.last_stats["kernel_variant"]
+
+
+def test_a_refused_call_leaves_the_population_as_it_was():
+    import ctypes as C
+
+    _lib, envs, _, QLearningPopulation, *_ = _product()
+    lib = _lib.load()
+    M = TINY[0]
+    pop, env = _tiny()
+    res = pop.run_steps(60, env)
+    assert res.episode_counts.sum() > 0 and res.returns.size == res.episode_counts.sum()
+    other = QLearningPopulation(*TINY, dtype=np.float32)
+    foreign = envs.HashTabularEnv(*TINY)
+    foreign.bind(other)
+
+    def state():
+        eps, lr = np.empty(M), np.empty(M)
+        _lib.check(lib.qe_population_schedules(pop.handle, _lib.ptr(eps, C.c_double), _lib.ptr(lr, C.c_double)))
+        return [pop.step_counters, eps, lr, pop.q_tables]
+
+    before = state()
+    st = _lib.RolloutStats()
+    h, ev = pop.handle, env.handle
+    for call, text in (
+            (lambda: lib.qe_population_rollout(h, ev, -1, _lib.LEARN_ITER, 1, C.byref(st), *[None] * 6), "steps must be >= 0"),
+            (lambda: lib.qe_population_rollout(h, ev, 5, 2, 1, C.byref(st), *[None] * 6), "bad learn mode"),
+            (lambda: lib.qe_population_rollout(h, foreign.handle, 5, _lib.LEARN_ITER, 1, C.byref(st), *[None] * 6), "engine/env mismatch"),
+            (lambda: lib.qe_population_evaluate(h, ev, 5, -1, 1, C.byref(st), *[None] * 4), "episodes must be >= 0")):
+        assert lib.qe_population_log(h, 0, None, None) == res.returns.size  # the log of the latest accepted call
+        st.kernel_ms, st.launches, st.kernel_variant = 1.0, 1, 1
+        assert call() == _lib.ERR_INVALID
+        assert lib.qe_last_error().decode() == text
+        assert not any(getattr(st, f) for f, _ in st._fields_), text
+        assert lib.qe_population_log(h, 0, None, None) == 0, text
+        for got, want in zip(state(), before):
+            assert np.array_equal(got, want), text
+        res = pop.run_steps(60, env, res.state_dict)  # ... and the population runs on
+        before = state()
+        assert res.returns.size > 0
+
+
+@pytest.mark.parametrize(("kw", "variant"), METHODS)
+def test_a_zero_step_call_moves_nothing_under_every_method(kw, variant):
+    pop, env = _tiny(**kw)
+    pop.step_counter = 11
+    res = pop.run_steps(0, env)
+    assert pop.last_stats["launches"] == 0 and pop.last_stats["kernel_variant"] == variant
+    assert pop.step_counter == 11 and res.state_dict["rng_step"] == 11
+    assert not res.episode_counts.any() and res.returns.size == 0
+    sd = res.state_dict
+    assert ("pending_actions" in sd) == (kw.get("update_rule") == "sarsa")
+    assert ("n_step_window" in sd) == ("n_step" in kw) and ("eligibility_traces" in sd) == ("trace_decay" in kw)
+    if "pending_actions" in sd:
+        assert (sd["pending_actions"] == -1).all()
+    if "n_step_window" in sd:
+        assert not any(v.any() for v in sd["n_step_window"].values())
+    if "eligibility_traces" in sd:
+        assert not any(v.any() for v in sd["eligibility_traces"].values())
+    if pop.planning_steps:
+        model = pop.planning_model
+        assert not model["count"].any() and (model["next_states"] == -1).all() and (model["visited"] == -1).all()
+    after = pop.run_steps(20, env, sd)
+    fresh, fresh_env = _tiny(**kw)
+    fresh.step_counter = 11
+    _same_call(pop, after, fresh, fresh.run_steps(20, fresh_env))
+    assert pop.last_stats["launches"] > 0 and pop.step_counter == 31
+
+
+@pytest.mark.parametrize("method", ["n_step", "traces", "planning"])
+def test_a_method_switched_off_and_on_again_starts_from_nothing(method):
+    import ctypes as C
+
+    _lib, *_ = _product()
+    lib = _lib.load()
+    M = TINY[0]
+    kw = {"n_step": {"update_rule": "sarsa", "n_step": 3}, "traces": {"update_rule": "sarsa", "trace_decay": 0.5, "trace_length": 4},
+          "planning": {"planning_steps": 2}}[method]
+    pop, env = _tiny(**kw)
+    first = pop.run_steps(5, env)
+    tables, h = pop.q_tables, pop.handle
+    if method == "n_step":
+        assert first.state_dict["n_step_window"]["length"].any()
+        assert lib.qe_population_set_n_step(h, 1) == 0 and lib.qe_population_n_step(h) == 1
+        assert lib.qe_population_set_n_step(h, 3) == 0 and lib.qe_population_n_step(h) == 3
+        assert not any(v.any() for v in pop.n_step_window.values())
+    elif method == "traces":
+        assert first.state_dict["eligibility_traces"]["values"].any()
+        assert lib.qe_population_set_traces(h, 0, 0, None) == 0 and lib.qe_population_trace_config(h, None, None, None) == 0
+        assert lib.qe_population_set_traces(h, 4, 0, _lib.ptr(np.full(M, 0.5), C.c_double)) == 0
+        assert lib.qe_population_trace_config(h, None, None, None) == 1
+        assert not any(v.any() for v in pop.eligibility_traces.values())
+    else:
+        assert pop.planning_model["count"].all()
+        assert lib.qe_population_set_planning(h, 0) == 0 and lib.qe_population_planning(h) == 0
+        assert lib.qe_population_set_planning(h, 2) == 0 and lib.qe_population_planning(h) == 2
+        model = pop.planning_model
+        assert not model["count"].any() and (model["next_states"] == -1).all() and (model["visited"] == -1).all()
+    # the environment, the schedules, the counters and SARSA's pending action go on; the method's own state does not
+    sd = {k: v for k, v in first.state_dict.items() if k not in ("n_step_window", "eligibility_traces")}
+    second = pop.run_steps(5, env, dict(sd))
+    fresh, fresh_env = _tiny(**kw)
+    fresh.set_q_tables(tables)
+    fresh.restore_training_state(sd)
+    _same_call(pop, second, fresh, fresh.run_steps(5, fresh_env, dict(sd)))
+    assert pop.step_counter == 10 and not np.array_equal(pop.q_tables, tables)
