@@ -37,6 +37,9 @@ RULE_Q_LEARNING, RULE_SARSA, RULE_EXPECTED_SARSA = 0, 1, 2  # qe_update_rule
 N_STEP_MAX = 16  # qe_population_set_n_step
 TRACE_MAX = 32  # qe_population_set_traces
 PLANNING_MAX = 64  # qe_population_set_planning
+# qe_population_set_visits: the (table dtype, 16-byte loads per fp32 row) builds of k_visit_rollout that are NOT compiled
+# because they do not fit the register file without scratch (visit_supported in csrc/qe_host.h)
+VISIT_REFUSED = frozenset()
 TRACE_REPLACING, TRACE_ACCUMULATING = 0, 1  # qe_trace_kind
 TRACE_KINDS = {"replacing": TRACE_REPLACING, "accumulating": TRACE_ACCUMULATING}
 UPDATE_RULES = {"q_learning": RULE_Q_LEARNING, "sarsa": RULE_SARSA, "expected_sarsa": RULE_EXPECTED_SARSA}
@@ -54,7 +57,9 @@ def decode_variant(v: int) -> dict:
     ``k_trace_rollout``) is the population with eligibility traces: the rule in bits 4-5 (0 = Q-learning, Watkins's
     Q(lambda); 1 = SARSA(lambda)), ``trace_length`` in bits 24-29 and ``trace_kind`` in bit 30 (0 and None on every other
     path).  Path 13 (``population_dyna``, kernel ``k_dyna_rollout``) is the Q-learning population with Dyna-Q: NV and
-    masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has."""
+    masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has.  Path 14
+    (``population_visit``, kernel ``k_visit_rollout``) is the Q-learning population with visit counts: NV and masked as path
+    6, ``visit_lr`` in bit 4 and ``bonus`` (some run's beta is above 0) in bit 5, two keys that only this path's dict has."""
     v = int(v)
     nstep = (v & 15) == 11
     trace = (v & 15) == 12
@@ -62,7 +67,7 @@ def decode_variant(v: int) -> dict:
     out = {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
                  7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval",
-                 11: "population_nstep", 12: "population_trace", 13: "population_dyna"}.get(v & 15, "none"),
+                 11: "population_nstep", 12: "population_trace", 13: "population_dyna", 14: "population_visit"}.get(v & 15, "none"),
         "rule": ({1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td
                  else {0: "q_learning", 1: "sarsa"}.get((v >> 4) & 3, "none") if trace else "q_learning"),
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
@@ -73,7 +78,16 @@ def decode_variant(v: int) -> dict:
     }
     if (v & 15) == 13:
         out["planning_steps"] = (v >> 24) & 127
+    if (v & 15) == 14:
+        out["visit_lr"] = bool((v >> 4) & 1)
+        out["bonus"] = bool((v >> 5) & 1)
     return out
+
+
+def visit_build_shipped(dtype, action_size: int) -> bool:
+    """Whether ``k_visit_rollout`` is built for rows of ``action_size`` actions of ``dtype`` (``VISIT_REFUSED``)."""
+    nv = max(4, 1 << (int(action_size) - 1).bit_length()) // 4
+    return (np.dtype(dtype).name, nv) not in VISIT_REFUSED
 
 
 def variant_symbol(v: int, dtype: str = "float", env: str = "HashEnv", lanes_per_row: int = 4, vec: bool = False) -> str:
@@ -238,6 +252,11 @@ PROTOTYPES = {
     "qe_population_planning": (C.c_int, [_P]),
     "qe_population_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
     "qe_population_set_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
+    "qe_population_set_visits": (C.c_int, [_P, _F64P, C.c_int32]),
+    "qe_population_visits": (C.c_int, [_P, _I32P, _I32P, _F64P]),
+    "qe_population_visit_counts": (C.c_int, [_P, _U32P]),
+    "qe_population_set_visit_counts": (C.c_int, [_P, _U32P]),
+    "qe_population_visit_bonus": (C.c_int, [_P, _P, C.c_int32]),
     "qe_env_table_solve": (C.c_int, [_P, C.c_double, C.c_double, C.c_int32, _F64P, _F64P, _I32P, _F64P]),
     "qe_population_policy_values": (C.c_int, [_P, _P, _F64P, C.c_double, C.c_int32, _F64P, _I32P, _F64P, _U32P]),
     "qe_debug_occupy_cus": (C.c_int, [_P, C.c_int32, C.c_int32]),

@@ -57,6 +57,18 @@ it is NOT in the state dict.  :attr:`planning_model` reads and sets it, ``save_m
 ``.npz``.  A fresh process resumes with ``load`` (tables), ``load_model`` (model) and ``restore_training_state`` (counters,
 schedules), then passes the state dict to ``run_steps``.  ``double_q=True``, ``n_step > 1`` and ``trace_decay`` are
 refused with planning.  DESIGN section 4.3c defines the step; ``tests/dyna_model.py`` restates it on the oracle.
+
+``exploration_bonus=beta`` (one beta >= 0 or one per run) and ``visit_lr=True`` (Q-learning only; kernel
+``k_visit_rollout``) turn on per-cell visit counts ``N(s, a)``, the directed-exploration lever next to epsilon.  The pick
+sees ``Q[s, :] + beta / sqrt(N[s, :])`` instead of the Q-row (count-based optimism, MBIE-EB: an untried action has an
+infinite bonus and goes first), the target stays ``max Q`` and the prediction ``Q[s, a]``; ``visit_lr`` divides the
+step's learning rate by the incremented ``N[s, a]``, the sample-average rate ``1/N``.  The square root and the divisions
+are float64 and correctly rounded, so the runs equal a NumPy model bit for bit.  Counts are knowledge, like the tables
+and the Dyna model: they outlive calls and environment resets, greedy evaluation neither reads nor writes them, and they
+are NOT in the state dict.  :attr:`visit_counts` reads and sets them, :attr:`visit_bonus` reads the bonus the next pick
+adds.  A fresh process resumes with ``load`` (tables), ``pop.visit_counts = ...`` and ``restore_training_state``.  The
+other rules, ``double_q=True``, ``n_step > 1``, ``trace_decay`` and ``planning_steps > 0`` are refused with counting.
+DESIGN section 4.3c defines the step; ``tests/visit_model.py`` restates it on the oracle.
 """
 
 from __future__ import annotations
@@ -245,6 +257,22 @@ def model_arrays(model, runs, state_size, action_size) -> tuple | None:
     return _spec_arrays("planning_model", model, _model_specs(runs, state_size, action_size), exact=True)
 
 
+def visit_count_array(counts, runs, state_size, action_size) -> np.ndarray | None:
+    """``visit_counts`` as the uint32 ``[runs, S, A]`` array the library takes (None: every count zero): integers in
+    ``[0, 2^32)`` of exactly that shape; ``ValueError`` on anything else."""
+    if counts is None:
+        return None
+    arr = np.asarray(counts)
+    shape = (runs, state_size, action_size)
+    if arr.shape != shape or arr.dtype.kind not in "iu":
+        msg = f"visit_counts: expected shape {shape} of uint32, got shape {arr.shape} of {arr.dtype}"
+        raise ValueError(msg)
+    if arr.size and (arr.min() < 0 or arr.max() >= 2 ** 32):
+        msg = f"visit_counts: expected shape {shape} of uint32, got values outside [0, 2^32)"
+        raise ValueError(msg)
+    return np.ascontiguousarray(arr, dtype=np.uint32)
+
+
 # The per-run state a training call hands to the next one through the state dict: the dict's key, which is also the
 # population's property, and whether a population carries it.  (The planning model is knowledge, not such state.)
 _CARRIED = {"pending_actions": lambda pop: pop.update_rule == "sarsa", "n_step_window": lambda pop: pop.n_step > 1,
@@ -275,13 +303,16 @@ class QLearningPopulation:
     ``trace_decay`` (None: no traces; else one lambda in [0, 1] or a sequence of ``runs``) turns on eligibility traces for
     "sarsa" and "q_learning", with ``trace_length`` slots per run (1 .. 32) of ``trace_kind`` "replacing" or
     "accumulating".  ``planning_steps`` (0: none; 1 .. 64) turns on Dyna-Q for "q_learning": that many planning updates
-    from the run's learned model after every step (:attr:`planning_model`).  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
+    from the run's learned model after every step (:attr:`planning_model`).  ``exploration_bonus`` (None: none; else one
+    finite beta >= 0 or a sequence of ``runs``) adds ``beta / sqrt(N(s, a))`` to the row the pick sees and ``visit_lr=True``
+    divides the learning rate by ``N(s, a)``; either turns on the visit counts (:attr:`visit_counts`), for "q_learning"
+    without ``double_q``, ``n_step``, ``trace_decay`` or ``planning_steps``.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
     call they are left advanced (``set_value``), as :class:`GpuRolloutQLearning` leaves them."""
 
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
                  update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
-                 trace_kind="replacing", planning_steps=0):
+                 trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -327,6 +358,43 @@ class QLearningPopulation:
             if self.state_size * self.action_size >= 2 ** 31:
                 msg = f"planning_steps={planning_steps}: state_size * action_size must be below 2^31"
                 raise ValueError(msg)
+        if not isinstance(visit_lr, (bool, np.bool_)):
+            msg = f"visit_lr must be a bool, got {visit_lr!r}"
+            raise ValueError(msg)
+        self.exploration_bonus = None
+        self.visit_lr = bool(visit_lr)
+        if exploration_bonus is not None or self.visit_lr:
+            what = "exploration_bonus" if exploration_bonus is not None else "visit_lr"
+            if update_rule != "q_learning":
+                msg = (f"{what} needs update_rule='q_learning', got {update_rule!r}: the bonus changes the behaviour policy "
+                       "only; the on-policy rules under a bonus policy are not built")
+                raise ValueError(msg)
+            if double_q:
+                msg = f"{what} with double_q=True: visit counts are built for the one-table Q-learning step"
+                raise ValueError(msg)
+            if n_step > 1:
+                msg = f"{what} with n_step={n_step}: visit counts are built for the one-step rule"
+                raise ValueError(msg)
+            if trace_decay is not None:
+                msg = f"{what} with trace_decay: visit counts are built for the one-step rule"
+                raise ValueError(msg)
+            if planning_steps > 0:
+                msg = f"{what} with planning_steps={planning_steps}: visit counts are built for the step without planning"
+                raise ValueError(msg)
+            per_run = _per_run(0.0 if exploration_bonus is None else exploration_bonus, self.runs, "exploration_bonus")
+            try:
+                beta = np.ascontiguousarray(per_run, dtype=np.float64)
+            except (TypeError, ValueError) as err:
+                msg = f"exploration_bonus must be None, a finite number >= 0 or a sequence of {self.runs}, got {exploration_bonus!r}"
+                raise ValueError(msg) from err
+            if beta.shape != (self.runs,) or not (np.isfinite(beta) & (beta >= 0)).all():
+                msg = f"exploration_bonus: every beta must be a finite number >= 0, got {exploration_bonus!r}"
+                raise ValueError(msg)
+            if not _lib.visit_build_shipped(self.dtype, self.action_size):
+                msg = (f"visit counts: the kernel for {self.dtype} rows of {self.action_size} actions is not built (it does not "
+                       "fit the register file)")
+                raise ValueError(msg)
+            self.exploration_bonus = beta
         self.planning_steps = int(planning_steps)
         self.update_rule = update_rule
         self.double_q = bool(double_q)
@@ -396,6 +464,9 @@ class QLearningPopulation:
                                                           _lib.ptr(self.trace_decay, C.c_double)))
         if self.planning_steps:
             _lib.check(self._lib.qe_population_set_planning(self._h, self.planning_steps))
+        if self.counting:
+            _lib.check(self._lib.qe_population_set_visits(self._h, _lib.ptr(self.exploration_bonus, C.c_double),
+                                                         1 if self.visit_lr else 0))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -521,6 +592,42 @@ class QLearningPopulation:
                 raise ValueError(msg)
             return
         self._set_state(self._lib.qe_population_set_model, model_arrays(model, self.runs, self.state_size, self.action_size), 5)
+
+    @property
+    def counting(self) -> bool:
+        """Whether the population keeps visit counts (``exploration_bonus is not None or visit_lr``)."""
+        return self.exploration_bonus is not None
+
+    @property
+    def visit_counts(self) -> np.ndarray | None:
+        """Counting on: ``N(s, a)`` of every run, uint32 ``[runs, S, A]`` -- how often the run has taken the action in
+        the state during training, saturating at ``2^32 - 1``.  Off: None.  Setting None forgets everything; anything but
+        integers in ``[0, 2^32)`` of that shape is a ``ValueError``."""
+        if not self.counting:
+            return None
+        out = np.empty((self.runs, self.state_size, self.action_size), dtype=np.uint32)
+        _lib.check(self._lib.qe_population_visit_counts(self._h, _lib.ptr(out, C.c_uint32)))
+        return out
+
+    @visit_counts.setter
+    def visit_counts(self, counts) -> None:
+        if not self.counting:
+            if counts is not None:
+                msg = "a population without exploration_bonus or visit_lr has no visit counts"
+                raise ValueError(msg)
+            return
+        arr = visit_count_array(counts, self.runs, self.state_size, self.action_size)
+        _lib.check(self._lib.qe_population_set_visit_counts(self._h, _lib.ptr(arr, C.c_uint32)))
+
+    @property
+    def visit_bonus(self) -> np.ndarray | None:
+        """Counting on: the bonus the next pick adds to every cell, table dtype ``[runs, S, A]``: 0 where the run's beta
+        is 0, else ``dtype(beta / sqrt(float64(N)))`` (``+inf`` at an untried cell).  Off: None."""
+        if not self.counting:
+            return None
+        out = np.empty((self.runs, self.state_size, self.action_size), dtype=self.dtype)
+        _lib.check(self._lib.qe_population_visit_bonus(self._h, out.ctypes.data, self._dtype_code))
+        return out
 
     def save_model(self, filename) -> None:
         """:attr:`planning_model` as one ``.npz`` (``ValueError`` without planning)."""
@@ -876,4 +983,4 @@ class QLearningPopulation:
 
 
 __all__ = ["PolicyValues", "PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "window_arrays"]
+           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "visit_count_array", "window_arrays"]

@@ -30,6 +30,7 @@ struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
 template <typename T>
 struct TraceSlots;  // the slots of the eligibility traces (qe_rollout_trace.h)
 struct DynaModel;   // the learned model and visited list of Dyna-Q (qe_rollout_dyna.h)
+struct VisitPlanes; // the visit counts and the bonus plane (qe_rollout_visit.h)
 }
 
 // records the text qe_last_error() returns (thread-local) and hands `code` back
@@ -236,10 +237,26 @@ struct PopState {
             planning = 0;
         }
     } dyna;
+    // Visit counts (qe_population_set_visits): off = the kernels above.  On: every run's counts N, uint32, and the
+    // derived bonus plane B = bonus(beta, N) in the table dtype, both indexed like the table ([runs * S, ld]; the
+    // padding columns of B hold 0), and every run's beta (k_visit_rollout, qe_rollout_visit.h); allocated when counting
+    // is set, kept until it is set off.  After every call B == bonus(beta, N) in every cell.
+    struct Visits {
+        bool on = false, lr = false, any_bonus = false;
+        DevBuf<uint32_t> n;
+        DevBuf<uint8_t> b;             // runs * S * ld values of the table dtype, as bytes
+        DevBuf<double> beta;
+        std::vector<double> h_beta;
+        void release() {
+            n.release(); b.release(); beta.release();
+            h_beta.clear();
+            on = lr = any_bonus = false;
+        }
+    } visit;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
-        log.release(); epi.release(); win.release(); trace.release(); dyna.release();
+        log.release(); epi.release(); win.release(); trace.release(); dyna.release(); visit.release();
         step_off.release(); pending.release();
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
@@ -469,7 +486,8 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   and n in bits 24-28, which no other path uses; path 12 = population with eligibility traces (k_trace_rollout): the
 //   rule in bits 4-5 (0 = Watkins's Q(lambda), 1 = SARSA(lambda)), NV and masked as path 6, K in bits 24-29 and the trace
 //   kind in bit 30, which no other field of that path uses; path 13 = population with Dyna-Q (k_dyna_rollout): NV and
-//   masked as path 6, and the planning updates per step in bits 24-30
+//   masked as path 6, and the planning updates per step in bits 24-30; path 14 = population with visit counts
+//   (k_visit_rollout): NV and masked as path 6, visit_lr in bit 4 and "some beta > 0" in bit 5
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -482,6 +500,7 @@ constexpr int64_t QE_VARIANT_RUNS_DOUBLE_EVAL = 10;  // ... and its greedy evalu
 constexpr int64_t QE_VARIANT_RUNS_NSTEP = 11;  // population, n-step SARSA / Expected SARSA (k_nstep_rollout): as path 8, + n in bits 24-28
 constexpr int64_t QE_VARIANT_RUNS_DYNA = 13;   // population, Dyna-Q (k_dyna_rollout): NV and masked bits, + planning updates in bits 24-30
 constexpr int64_t QE_VARIANT_RUNS_TRACE = 12;  // population, SARSA(lambda) / Watkins's Q(lambda) (k_trace_rollout): + K in bits 24-29, kind in bit 30
+constexpr int64_t QE_VARIANT_RUNS_VISIT = 14;  // population, visit counts (k_visit_rollout): NV and masked bits, + visit_lr in bit 4, bonus in bit 5
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -549,6 +568,13 @@ int64_t launch_trace_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, co
 // ... with Dyna-Q: Q-learning's step, then w.n planning updates from the runs' learned models (qe_inst_runs_dyna.hip)
 template <typename T, class Env>
 int64_t launch_dyna_runs(const RunsLaunch<T>& l, const DynaModel& w);
+// ... with visit counts: Q-learning's step with the bonus plane on the pick and, optionally, the 1/N rate
+// (qe_inst_runs_visit.hip); `any_bonus`: some run's beta is above 0 (bit 5 of the variant)
+template <typename T, class Env>
+int64_t launch_visit_runs(const RunsLaunch<T>& l, const VisitPlanes& w, bool any_bonus);
+// The (table dtype, NV) builds of k_visit_rollout that are compiled: the kernel holds two rows, and a build ships only
+// if it fits the register file without scratch (DESIGN 4.3c lists the others; qe_population_set_visits refuses them).
+constexpr bool visit_supported(bool f32, int nv) { return true; }
 // ... and one launch of its greedy evaluation (episodes == 0: step mode; else used / done per run, see k_evaluate_runs)
 template <typename T, class Env>
 int64_t launch_evaluate_runs(const RunsLaunch<T>& l, long long episodes, long long* used, uint8_t* done);

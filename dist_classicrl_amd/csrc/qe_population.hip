@@ -6,6 +6,7 @@
 #include "qe_rollout_dyna.h"
 #include "qe_rollout_nstep.h"
 #include "qe_rollout_trace.h"
+#include "qe_rollout_visit.h"
 
 namespace {
 
@@ -240,6 +241,28 @@ int model_clear(qe_engine* e) {
     return QE_OK;
 }
 
+// Visit counts: the bonus plane rewritten from the counts and the runs' betas (k_visit_fill), so that B == bonus(beta, N)
+// in every cell; synchronises the stream.
+int visits_fill(qe_engine* e) {
+    PopState& P = e->pop;
+    const int64_t per_run = P.S * (int64_t)e->ld, total = P.runs * per_run;
+    const dim3 grid(grid_for(total, 256)), block(256);
+    if (e->dtype == QE_F32)
+        hipLaunchKernelGGL(k_visit_fill<float>, grid, block, 0, e->stream, (const uint32_t*)P.visit.n.p, (float*)P.visit.b.p,
+                           (const double*)P.visit.beta.p, per_run, total, (int)e->A, (int)e->ld);
+    else
+        hipLaunchKernelGGL(k_visit_fill<double>, grid, block, 0, e->stream, (const uint32_t*)P.visit.n.p, (double*)P.visit.b.p,
+                           (const double*)P.visit.beta.p, per_run, total, (int)e->A, (int)e->ld);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+// What every other mode setter answers while visit counts are on.
+int visits_refuse(const char* what) {
+    return qe_fail(QE_ERR_UNSUPPORTED, "%s: visit counts are on, and they are built for the plain one-step Q-learning run (qe_population_set_visits)", what);
+}
+
 // The double estimator's table entry points: the qe_table_* call `f` with table B standing in for the engine's table.
 template <class F>
 int on_table_b(qe_engine* e, F f) {
@@ -269,6 +292,8 @@ void slots_to_device(const V* abi, U* dev, size_t m, size_t w, Keep keep) {
 template <typename T, class Env>
 int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
     const PopState& P = e->pop;
+    if (P.visit.on)
+        return launch_visit_runs<T, Env>(l, VisitPlanes{P.visit.n.p, P.visit.b.p, P.visit.beta.p, P.visit.lr ? 1 : 0}, P.visit.any_bonus);
     if (P.table_b) return launch_double_runs<T, Env>(l, (T*)P.table_b);
     if (P.dyna.planning)
         return launch_dyna_runs<T, Env>(l, DynaModel{P.dyna.planning, P.dyna.entry.p, P.dyna.visited.p, P.dyna.count.p, P.S * (int64_t)e->A});
@@ -580,6 +605,7 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
     if (int rc = need_population(e)) return rc;
     if (rule != QE_RULE_Q_LEARNING && rule != QE_RULE_SARSA && rule != QE_RULE_EXPECTED_SARSA)
         return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
+    if (e->pop.visit.on && rule != QE_RULE_Q_LEARNING) return visits_refuse("an on-policy update rule");
     if (e->pop.table_b && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (qe_population_set_double)");
     if (e->pop.win.n > 1 && rule == QE_RULE_Q_LEARNING)
@@ -608,6 +634,7 @@ int qe_population_update_rule(qe_engine* e) {
 int qe_population_set_double(qe_engine* e, int32_t on) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
+    if (on && P.visit.on) return visits_refuse("the double estimator");
     if (on && P.win.n > 1)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.win.n);
     if (on && P.trace.k)
@@ -701,6 +728,7 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
     if (n < 1 || n > NSTEP_MAX) return qe_fail(QE_ERR_INVALID, "n_step must be in 1 .. %d, got %d", NSTEP_MAX, (int)n);
+    if (n > 1 && P.visit.on) return visits_refuse("n_step > 1");
     if (n > 1 && P.rule == QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "n_step = %d with Q-learning: an uncorrected n-step Q-learning is not an off-policy method (importance "
@@ -806,6 +834,7 @@ int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double
     if (K < 1 || K > TRACE_MAX) return qe_fail(QE_ERR_INVALID, "trace_length must be in 1 .. %d, got %d", TRACE_MAX, (int)K);
     if (kind != QE_TRACE_REPLACING && kind != QE_TRACE_ACCUMULATING)
         return qe_fail(QE_ERR_INVALID, "unknown trace kind %d (qe_trace_kind)", (int)kind);
+    if (P.visit.on) return visits_refuse("eligibility traces");
     for (size_t r = 0; r < m; ++r)
         if (!(lambda[r] >= 0.0 && lambda[r] <= 1.0))
             return qe_fail(QE_ERR_UNSUPPORTED, "trace decay of run %lld: lambda = %g is outside [0, 1]", (long long)r, lambda[r]);
@@ -918,6 +947,7 @@ int qe_population_set_planning(qe_engine* e, int32_t n) {
         P.dyna.release();
         return QE_OK;
     }
+    if (P.visit.on) return visits_refuse("planning");
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "planning with update rule %d: Dyna-Q replays remembered transitions through Q-learning's update; planning "
@@ -1046,6 +1076,121 @@ int qe_population_set_model(qe_engine* e, const int32_t* next_states, const floa
     HIP_TRY(hipMemcpyAsync(P.dyna.visited.p, hv.data(), hv.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(P.dyna.count.p, count, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+int qe_population_set_visits(qe_engine* e, const double* bonus, int32_t visit_lr) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    PopState::Visits& V = P.visit;
+    const size_t m = (size_t)P.runs;
+    if (!bonus && !visit_lr) {  // off: the counts are forgotten
+        if (!V.on) return QE_OK;
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        V.release();
+        return QE_OK;
+    }
+    if (P.rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "visit counts with update rule %d: the bonus changes the behaviour policy only, and the on-policy rules "
+                       "under a bonus policy are not built",
+                       P.rule);
+    if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: the double estimator is on (qe_population_set_double)");
+    if (P.win.n > 1) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts with n_step = %d: they are built for the one-step rule (qe_population_set_n_step)", P.win.n);
+    if (P.trace.k) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: eligibility traces are on (qe_population_set_traces)");
+    if (P.dyna.planning) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: planning is on (qe_population_set_planning)");
+    bool any = false;
+    for (size_t r = 0; bonus && r < m; ++r) {
+        if (!(bonus[r] >= 0.0) || std::isinf(bonus[r]))
+            return qe_fail(QE_ERR_UNSUPPORTED, "exploration bonus of run %lld: beta = %g is negative or not finite", (long long)r, bonus[r]);
+        any |= bonus[r] > 0.0;
+    }
+    if (e->ld > 64 || !visit_supported(e->dtype == QE_F32, e->ld / 4))
+        return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: the kernel for %s rows of %d actions is not built (it does not fit the register file)",
+                       e->dtype == QE_F32 ? "float32" : "float64", (int)e->A);
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t cells = m * (size_t)P.S * (size_t)e->ld;
+    if (!V.on) {  // (already on: the counts are knowledge and stay)
+        hipError_t err = V.n.ensure(cells);
+        if (err == hipSuccess) err = V.b.ensure(cells * e->esize());
+        if (err == hipSuccess) err = V.beta.ensure(m);
+        if (err == hipSuccess) err = hipMemsetAsync(V.n.p, 0, cells * sizeof(uint32_t), e->stream);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            V.release();
+            return qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "visit counts: the planes could not be allocated: %s",
+                           hipGetErrorString(err));
+        }
+    }
+    V.h_beta.assign(m, 0.0);
+    if (bonus) std::copy(bonus, bonus + m, V.h_beta.begin());
+    HIP_TRY(hipMemcpyAsync(V.beta.p, V.h_beta.data(), m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    V.on = true;
+    V.lr = visit_lr != 0;
+    V.any_bonus = any;
+    return visits_fill(e);
+}
+
+int qe_population_visits(qe_engine* e, int32_t* on, int32_t* visit_lr, double* bonus) {
+    if (int rc = need_population(e)) return rc;
+    const PopState::Visits& V = e->pop.visit;
+    if (on) *on = V.on ? 1 : 0;
+    if (visit_lr) *visit_lr = V.on && V.lr ? 1 : 0;
+    if (bonus && V.on) std::copy(V.h_beta.begin(), V.h_beta.end(), bonus);
+    return QE_OK;
+}
+
+int qe_population_visit_counts(qe_engine* e, uint32_t* out) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.visit.on) return qe_fail(QE_ERR_INVALID, "visit counts are off (qe_population_set_visits)");
+    if (!out) return qe_fail(QE_ERR_INVALID, "out is NULL");
+    const size_t rows = (size_t)P.runs * (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> h(rows * ld);
+    HIP_TRY(hipMemcpyAsync(h.data(), P.visit.n.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < rows; ++i) std::copy(h.begin() + i * ld, h.begin() + i * ld + A, out + i * A);
+    return QE_OK;
+}
+
+int qe_population_set_visit_counts(qe_engine* e, const uint32_t* in) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.visit.on) return qe_fail(QE_ERR_INVALID, "visit counts are off (qe_population_set_visits)");
+    const size_t rows = (size_t)P.runs * (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!in) {
+        HIP_TRY(hipMemsetAsync(P.visit.n.p, 0, rows * ld * sizeof(uint32_t), e->stream));
+        return visits_fill(e);
+    }
+    std::vector<uint32_t> h(rows * ld, 0u);  // (the padding columns hold 0)
+    for (size_t i = 0; i < rows; ++i) std::copy(in + i * A, in + i * A + A, h.begin() + i * ld);
+    HIP_TRY(hipMemcpyAsync(P.visit.n.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return visits_fill(e);
+}
+
+int qe_population_visit_bonus(qe_engine* e, void* out, int32_t dtype) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.visit.on) return qe_fail(QE_ERR_INVALID, "visit counts are off (qe_population_set_visits)");
+    if (!out) return qe_fail(QE_ERR_INVALID, "out is NULL");
+    if (dtype != QE_F32 && dtype != QE_F64) return qe_fail(QE_ERR_INVALID, "bad dtype %d", (int)dtype);
+    const size_t rows = (size_t)P.runs * (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint8_t> h(rows * ld * e->esize());
+    HIP_TRY(hipMemcpyAsync(h.data(), P.visit.b.p, h.size(), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const float* const h32 = reinterpret_cast<const float*>(h.data());
+    const double* const h64 = reinterpret_cast<const double*>(h.data());
+    for (size_t i = 0; i < rows; ++i)
+        for (size_t a = 0; a < A; ++a) {
+            const double v = e->dtype == QE_F32 ? (double)h32[i * ld + a] : h64[i * ld + a];
+            if (dtype == QE_F32) ((float*)out)[i * A + a] = (float)v;
+            else ((double*)out)[i * A + a] = v;
+        }
     return QE_OK;
 }
 

@@ -102,7 +102,9 @@ typedef struct qe_rollout_stats {
                                 SARSA(lambda)), NV and masked as path 6, the slot count K in bits 24-29 and the trace
                                 kind (qe_trace_kind) in bit 30, which no other field of that path uses; path 13:
                                 population with Dyna-Q (qe_population_set_planning): NV and masked as path 6, and the
-                                planning updates per step in bits 24-30 */
+                                planning updates per step in bits 24-30; path 14: population with visit counts
+                                (qe_population_set_visits): NV and masked as path 6, visit_lr in bit 4 and "some run's
+                                beta is above 0" in bit 5 */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -422,7 +424,28 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         planning is off, and from the upload for a next state outside [0, S) that is not -1, a count
  *                         that differs from the number of seen cells, or a list entry (below count) that is out of range,
  *                         unseen in the model or listed twice; entries from count on and the rewards and flags of unseen
- *                         cells are not read. */
+ *                         cells are not read.
+ *   qe_population_set_visits  per-cell visit counts N(s, a) of every run, uint32, zero when counting is turned on, with a
+ *                         count-based optimism bonus and, with visit_lr != 0, the sample-average learning rate.  `bonus`
+ *                         holds every run's beta (NULL: all zero); NULL with visit_lr == 0 turns counting off and forgets
+ *                         the counts.  bonus(beta, N) = T(0) when beta == 0, else T(beta / sqrt(float64(N))): a float64
+ *                         square root and division and one rounding to the table dtype T; N == 0 gives +inf.  A training
+ *                         step is Q-learning's step with three changes: the pick (same draws, same selection variant)
+ *                         sees the score row Q[s, j] + bonus(beta, N[s, j]) -- one add in T over the valid columns, a NaN
+ *                         there like any other -- while the prediction stays Q[s, a]; after the environment step N[s, a]
+ *                         becomes N[s, a] + 1, saturating at 2^32 - 1 (a step without a selectable action counts at action
+ *                         0); with visit_lr the update takes lr / float64(N[s, a]), the incremented count, rounded to float
+ *                         on a float32 table as lr is.  The target stays the maximum of plain Q.  The counts are
+ *                         knowledge: they outlive calls and environment resets, and the evaluation calls neither read nor
+ *                         write them.  Turning counting on again while it is on keeps the counts.  Not a population engine
+ *                         -> QE_ERR_INVALID; a rule other than Q-learning, the double switch on, n_step > 1, traces on,
+ *                         planning on, a beta that is negative or not finite, or a (dtype, row stride) whose kernel is
+ *                         not built -> QE_ERR_UNSUPPORTED, and so is switching to any of those modes while counting is on.
+ *   qe_population_visits  whether counting is on, visit_lr, and (while on) every run's beta; any pointer may be NULL.
+ *   qe_population_visit_counts / qe_population_set_visit_counts  the counts, runs * S * A entries, run r's cell (s, a) at
+ *                         [(r * S + s) * A + a]; the upload takes NULL for "all zero" and rewrites the bonus plane.
+ *   qe_population_visit_bonus  the bonus the next pick adds to every cell, the same layout, as `dtype` (QE_F32 / QE_F64).
+ *                         The three are QE_ERR_INVALID while counting is off. */
 enum qe_trace_kind { QE_TRACE_REPLACING = 0, QE_TRACE_ACCUMULATING = 1 };
 enum qe_update_rule { QE_RULE_Q_LEARNING = 0, QE_RULE_SARSA = 1, QE_RULE_EXPECTED_SARSA = 2 };
 enum qe_run_schedule_kind { QE_SCHED_CONSTANT = 0, QE_SCHED_LINEAR = 1, QE_SCHED_EXPONENTIAL = 2 };
@@ -470,6 +493,11 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
                         int32_t* count);
 int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
                             const int32_t* visited, const int32_t* count);
+int qe_population_set_visits(qe_engine* e, const double* bonus /* [runs]; NULL: all zero */, int32_t visit_lr);
+int qe_population_visits(qe_engine* e, int32_t* on, int32_t* visit_lr, double* bonus);
+int qe_population_visit_counts(qe_engine* e, uint32_t* out);
+int qe_population_set_visit_counts(qe_engine* e, const uint32_t* in /* NULL: zero */);
+int qe_population_visit_bonus(qe_engine* e, void* out, int32_t dtype);
 
 /* ---- dynamic programming over a QE_ENV_TABLE environment (Sutton & Barto ch. 4; csrc/qe_mdp_solve.h) ------------------
  * The MDP is the law the environment samples from, read from its device records.  For (s, a) with k slots and a running

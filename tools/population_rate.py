@@ -4,7 +4,7 @@ rollout on the same environment, measured in the same process.
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
                                     [--rule q_learning|sarsa|expected_sarsa] [--n-step N] [--double] [--actions A]
                                     [--trace-decay LAMBDA [--trace-length K] [--trace-kind replacing|accumulating]]
-                                    [--planning-steps N]
+                                    [--planning-steps N] [--exploration-bonus B] [--visit-lr]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
@@ -22,6 +22,9 @@ DIR/population_rate_<rule>_trace<K>.json.
 --planning-steps N (1 .. 64, with --rule q_learning) trains with Dyna-Q (k_dyna_rollout): N planning updates from the
 run's learned model after every step; writes DIR/population_rate_dyna<N>.json, with the event time per table update
 (env-step time / (1 + N)) beside the time per env-step.
+--exploration-bonus B (B >= 0) and --visit-lr (with --rule q_learning) train with visit counts (k_visit_rollout): the
+bonus B / sqrt(N(s, a)) on the pick and / or the learning rate divided by N(s, a); writes DIR/population_rate_visit.json,
+with the event time per env-step beside the wall rate.
 --double trains (or, with --evaluate, evaluates) a Double Q-learning population (double_q=True: k_double_rollout /
 k_double_evaluate, two tables per run) against the same single-table standalone baseline and writes
 DIR/population_rate_double.json (DIR/population_eval_rate_double.json).
@@ -82,7 +85,7 @@ def schedules():
 
 
 def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1, traces=None,
-                    planning=0):
+                    planning=0, bonus=None, visit_lr=False):
     lr, eps = schedules()
     kw = {} if rule == "q_learning" else {"update_rule": rule}
     if n_step != 1:
@@ -93,6 +96,10 @@ def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", dou
         kw.update(trace_decay=traces[0], trace_length=traces[1], trace_kind=traces[2])
     if planning:
         kw["planning_steps"] = planning
+    if bonus is not None:
+        kw["exploration_bonus"] = bonus
+    if visit_lr:
+        kw["visit_lr"] = True
     pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
@@ -160,6 +167,8 @@ def main() -> None:
     ap.add_argument("--trace-length", type=int, default=16, help="trace slots per run (1 .. 32)")
     ap.add_argument("--trace-kind", choices=["replacing", "accumulating"], default="replacing")
     ap.add_argument("--planning-steps", type=int, default=0, help="Dyna-Q planning updates per step (0 .. 64; q_learning only)")
+    ap.add_argument("--exploration-bonus", type=float, default=None, help="beta of the count-based bonus beta / sqrt(N(s, a)) (q_learning only)")
+    ap.add_argument("--visit-lr", action="store_true", help="learning rate divided by the visit count N(s, a) (q_learning only)")
     ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
     if args.evaluate and args.rule != "q_learning":
@@ -173,6 +182,11 @@ def main() -> None:
     if args.planning_steps and (args.rule != "q_learning" or args.double or args.n_step != 1 or args.trace_decay is not None
                                 or args.evaluate):
         ap.error("--planning-steps goes with --rule q_learning (training runs), without --double, --n-step and --trace-decay")
+    counting = args.exploration_bonus is not None or args.visit_lr
+    if counting and (args.rule != "q_learning" or args.double or args.n_step != 1 or args.trace_decay is not None or args.planning_steps
+                     or args.evaluate):
+        ap.error("--exploration-bonus and --visit-lr go with --rule q_learning (training runs), without --double, --n-step, "
+                 "--trace-decay and --planning-steps")
     traces = None if args.trace_decay is None else (args.trace_decay, args.trace_length, args.trace_kind)
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
@@ -202,7 +216,11 @@ def main() -> None:
             pop = population_eval_rate(make_env, M, S, A, k, dtype, log, args.double)
         else:
             pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step, traces,
-                                  args.planning_steps)
+                                  args.planning_steps, args.exploration_bonus, args.visit_lr)
+            if counting:
+                pop["exploration_bonus"] = args.exploration_bonus
+                pop["visit_lr"] = args.visit_lr
+                pop["event_ns_per_env_step"] = pop["kernel_ms"] * 1e6 / (pop["runs"] * pop["steps"])
             if args.planning_steps:
                 pop["planning_steps"] = args.planning_steps
                 pop["event_ns_per_env_step"] = pop["kernel_ms"] * 1e6 / (pop["runs"] * pop["steps"])
@@ -222,6 +240,8 @@ def main() -> None:
         name = f"population_rate_{args.rule}_trace{args.trace_length}.json"
     if args.planning_steps:
         name = f"population_rate_dyna{args.planning_steps}.json"
+    if counting:
+        name = "population_rate_visit.json"
     if args.double:
         name = name.replace(".json", "_double.json")
     (args.out / name).write_text(json.dumps(lines, indent=1))
