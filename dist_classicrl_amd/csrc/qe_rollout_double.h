@@ -96,80 +96,43 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_double_rollout(RunsCtx<T> c, Env
     if (r >= c.M) return;
     T* const qa = c.q + r * c.S * (4 * NV);
     T* const qb = table_b + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;  // the draw key of every rollout: the environment's agent id
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     RowV<T, NV> z;
-    load_sum_row_lane<T, NV>(z, qa, qb, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_sum_row_lane<T, NV>(z, qa, qb, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool z_nan = row_nan_lane<NV>(masked_row<MASKED>(z, valid));
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps_v);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
+        const U4 x = lane.draws(step);
+        const bool explore = (unsigned long long)x.x < eps_threshold(lane.eps_v);
         T zpick;
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(z, valid), valid, explore, x.y, x.z, &zpick, nan_sel && z_nan);
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its tables
-            empty = true;
-            act = 0;
-        }
-        const int32_t s = n;
+        const int act = lane.select(masked_row<MASKED>(z, valid), valid, explore, x, z_nan, &zpick);
+        const int32_t s = lane.n;
         const bool coin = (x.w >> 31) != 0;
         T* const qx = coin ? qb : qa;
         const T* const qy = coin ? qa : qb;
         const int64_t cell = (int64_t)s * (4 * NV) + act;
         const T picked = qx[cell], other = qy[cell];
-        const Transition tr = Env::step(ev, r, s, aux, act, step);
-        n = tr.next_obs;
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
-        const T v = load_sum_row_argmax_lane<T, NV, M>(z, qx, qy, n, valid);
+        const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
+        const T v = load_sum_row_argmax_lane<T, NV, M>(z, qx, qy, lane.n, valid);
         z_nan = row_nan_lane<NV>(masked_row<MASKED>(z, valid));
-        h.lr = lr_v; h.lr32 = (float)lr_v;
+        lane.learning_rate(lane.lr_v);
         T u;
-        const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, h, c.mode, &u);
+        const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, lane.h, c.mode, &u);
         qx[cell] = q1;
-        if (n == s) {  // own write lands in the sum row held in registers
+        if (lane.n == s) {  // own write lands in the sum row held in registers
             // (a NaN z[a] stays one: a NaN in either cell, or inf + -inf, survives the update of X[s,a] -- so OR suffices)
             const T z1 = q1 + other;
             z_nan |= z1 != z1;
-#pragma unroll
-            for (int j = 0; j < 4 * NV; ++j) z.v[j] = j == act ? z1 : z.v[j];
+            patch_own_write<NV>(z, act, z1);
         }
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-        eps_v = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
-        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+        lane.episode_end(tr, t);
+        lane.advance_schedules();
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 // Greedy evaluation of every run of a double population: k_evaluate_runs with the sum row z in place of the row -- the
@@ -186,59 +149,36 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_double_evaluate(RunsCtx<T> c, En
     }
     const T* const qa = c.q + r * c.S * (4 * NV);
     const T* const qb = table_b + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
+    RunLane<T, NV, MASKED, false> lane(c, ev, r);
     bool empty = false, finished = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
 
     RowV<T, NV> z;
-    load_sum_row_lane<T, NV>(z, qa, qb, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_sum_row_lane<T, NV>(z, qa, qb, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     long long t = 0;
     while (t < steps) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
+        const U4 x = lane.draws(step);
         const RowV<T, NV> zm = masked_row<MASKED>(z, valid);
         T zpick;
-        int act = select_lane<T, NV, M>(zm, valid, false, x.y, x.z, &zpick, nan_sel && row_nan_lane<NV>(zm));
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its tables
-            empty = true;
-            act = 0;
-        }
-        const Transition tr = Env::step(ev, r, n, aux, act, step);
-        n = tr.next_obs;
-        acc += tr.reward;
+        int act = select_lane<T, NV, M>(zm, valid, false, x.y, x.z, &zpick, lane.nan_sel && row_nan_lane<NV>(zm));
+        empty |= lane.settle(act);
+        const Transition tr = Env::step(ev, r, lane.n, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        lane.acc += tr.reward;
         ++t;
         if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t - 1);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-            if (episodes && count >= episodes) {
+            lane.episode_done(t - 1);
+            if (episodes && lane.count >= episodes) {
                 finished = true;
                 break;
             }
         }
-        load_sum_row_lane<T, NV>(z, qa, qb, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+        load_sum_row_lane<T, NV>(z, qa, qb, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.empty = empty;
+    lane.store();
     if (episodes) {
         used[r] += t;
         if (finished) done[r] = 1;

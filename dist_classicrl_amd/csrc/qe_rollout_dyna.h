@@ -61,61 +61,40 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_dyna_rollout(RunsCtx<T> c, EnvCt
     int32_t* const visited = w.visited + r * w.cells;
     int32_t seen = w.count[r];
     const int plan = w.n;
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps_v);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
         T picked;
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, &picked, nan_sel && row_nan);
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-        }
-        const int32_t s = n;
+        const int act = lane.pick(row, valid, row_nan, step, lane.eps_v, &picked);
+        const int32_t s = lane.n;
         const int32_t cell = s * LD + act;
         const uint32_t known = model[cell].x;  // (in flight beside the environment step and the gather)
-        const Transition tr = Env::step(ev, r, s, aux, act, step);
-        n = tr.next_obs;
-        load_row_lane<NV>(row, q, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+        const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        load_row_lane<NV>(row, q, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
         const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
         row_nan = row_nan_lane<NV>(rowm);
         const T m = row_nan ? quiet_nan<T>() : row_max_lane(rowm);
-        h.lr = lr_v; h.lr32 = (float)lr_v;
+        lane.learning_rate(lane.lr_v);
         T u;
-        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, h, c.mode, &u);
+        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, lane.h, c.mode, &u);
         q[cell] = q1;
-        if (n == s) {  // own write lands in the row held in registers
+        if (lane.n == s) {  // own write lands in the row held in registers
             row_nan |= q1 != q1;
-#pragma unroll
-            for (int j = 0; j < LD; ++j) row.v[j] = j == act ? q1 : row.v[j];
+            patch_own_write<NV>(row, act, q1);
         }
         // 2. the model learns the outcome; a later outcome of the cell overwrites this one
         if (known == DYNA_UNSEEN) visited[seen++] = cell;
-        model[cell] = make_uint2((uint32_t)n | (tr.terminated ? 0x80000000u : 0u), __float_as_uint(tr.reward));
+        model[cell] = make_uint2((uint32_t)lane.n | (tr.terminated ? 0x80000000u : 0u), __float_as_uint(tr.reward));
         // 3. planning
         for (int i0 = 0; i0 < plan; i0 += DYNA_BATCH) {
-            const U4 y = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_PLAN | ((uint32_t)(i0 >> 2) << 8),
-                                       c.seed_lo, c.seed_hi);
+            const U4 y = lane.draws(step, STREAM_PLAN | ((uint32_t)(i0 >> 2) << 8));
             const uint32_t xs[DYNA_BATCH] = {y.x, y.y, y.z, y.w};
             int32_t o[DYNA_BATCH];
             uint2 e[DYNA_BATCH];
@@ -136,42 +115,22 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_dyna_rollout(RunsCtx<T> c, EnvCt
                     const RowV<T, NV> rpm = masked_row<MASKED>(rp, valid_mask_lane<Env, NV, MASKED>(ev, r, p));
                     const T mp = row_nan_lane<NV>(rpm) ? quiet_nan<T>() : row_max_lane(rpm);
                     T up;
-                    const T qn = Td<T>::apply(q0, rho, mp, term, h, c.mode, &up);
+                    const T qn = Td<T>::apply(q0, rho, mp, term, lane.h, c.mode, &up);
                     q[o[j]] = qn;
-                    if ((o[j] >> LOG_LD) == n) {  // the store lands in the row held in registers
+                    if ((o[j] >> LOG_LD) == lane.n) {  // the store lands in the row held in registers
                         patched = true;
                         const int col = o[j] & (LD - 1);
-#pragma unroll
-                        for (int k = 0; k < LD; ++k) row.v[k] = k == col ? qn : row.v[k];
+                        patch_own_write<NV>(row, col, qn);
                     }
                 }
             }
             if (patched) row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
         }
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-        eps_v = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
-        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+        lane.episode_end(tr, t);
+        lane.advance_schedules();
     }
     w.count[r] = seen;
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 }  // namespace qe

@@ -57,20 +57,7 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvC
     int32_t* const wa = ws + N * RUNS_BLOCK;
     float* const wr = reinterpret_cast<float*>(wa + N * RUNS_BLOCK);
     T* const q = c.q + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     // the window: entry i (0 = oldest) sits in slot at(i) of the ring that starts at slot `base`
     int base = 0, L = w.len[r];
@@ -84,30 +71,18 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvC
         return (k >= N ? k - N : k) * RUNS_BLOCK;
     };
 
-    auto pick = [&](const RowV<T, NV>& row, M valid, bool row_nan, unsigned long long step, double eps, T* value) -> int {
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps);
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, value, nan_sel && row_nan);
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-            *value = row.v[0];
-        }
-        return act;
-    };
-
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     int act = 0;
     if constexpr (RULE == TD_SARSA) {
         act = pending[r];
         T unused;
-        if (act < 0) act = pick(row, valid, row_nan, step0, eps_v, &unused);
+        if (act < 0) act = lane.pick_on_policy(row, valid, row_nan, lane.step0, lane.eps_v, &unused);
     }
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = step0 + (unsigned long long)t;
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
         // A window of n - 1 entries: this step updates entry 0 whatever happens (it pops, or the episode ends), and
         // nothing is stored before that update -- its prediction is loaded now, off the chain pick -> step -> gather
         const bool early = L == N - 1;
@@ -115,46 +90,45 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvC
         if (early) p0 = q[(int64_t)ws[at(0)] * (4 * NV) + wa[at(0)]];
         if constexpr (RULE == TD_EXPECTED_SARSA) {
             T unused;
-            act = pick(row, valid, row_nan, step, eps_v, &unused);
+            act = lane.pick_on_policy(row, valid, row_nan, step, lane.eps_v, &unused);
         }
-        const int32_t s = n;
-        const Transition tr = Env::step(ev, r, s, aux, act, step);
-        n = tr.next_obs;
+        const int32_t s = lane.n;
+        const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+        lane.n = tr.next_obs;
         {
             const int k = at(L);
             ws[k] = s; wa[k] = act; wr[k] = tr.reward;
             ++L;
         }
-        load_row_lane<NV>(row, q, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
-        const double eps_n = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
+        load_row_lane<NV>(row, q, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
+        const double eps_n = lane.next_eps();
         T v;
         if constexpr (RULE == TD_SARSA) {
             row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
-            act = pick(row, valid, row_nan, step + 1ull, eps_n, &v);
+            act = lane.pick_on_policy(row, valid, row_nan, step + 1ull, eps_n, &v);
         } else {
             const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
             row_nan = row_nan_lane<NV>(rowm);
             const T m = row_nan ? quiet_nan<T>() : row_max_lane(rowm);
             v = row_expected_lane<T, NV, M>(row, valid, m, eps_n);
         }
-        h.lr = lr_v; h.lr32 = (float)lr_v;
+        lane.learning_rate(lane.lr_v);
         const int updates = tr.terminated ? L : (L == N ? 1 : 0);
         for (int j = 0; j < updates; ++j) {
             T g = v;
-            for (int i = L - 1; i > j; --i) g = td_target(wr[at(i)], g, tr.terminated && i == L - 1, h, c.mode);
+            for (int i = L - 1; i > j; --i) g = td_target(wr[at(i)], g, tr.terminated && i == L - 1, lane.h, c.mode);
             const int k = at(j);
             const int32_t sj = ws[k], aj = wa[k];
             T* const cell = q + (int64_t)sj * (4 * NV) + aj;
             const T pred = (j == 0 && early) ? p0 : *cell;
             T u;
-            const T q1 = Td<T>::apply(pred, wr[k], g, tr.terminated && j == L - 1, h, c.mode, &u);
+            const T q1 = Td<T>::apply(pred, wr[k], g, tr.terminated && j == L - 1, lane.h, c.mode, &u);
             *cell = q1;
             if constexpr (RULE == TD_EXPECTED_SARSA) {
-                if (sj == n) {  // own write lands in the row held in registers
+                if (sj == lane.n) {  // own write lands in the row held in registers
                     row_nan |= q1 != q1;
-#pragma unroll
-                    for (int x = 0; x < 4 * NV; ++x) row.v[x] = x == aj ? q1 : row.v[x];
+                    patch_own_write<NV>(row, aj, q1);
                 }
             }
         }
@@ -165,19 +139,8 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvC
             base = base + 1 == N ? 0 : base + 1;
             --L;
         }
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-        eps_v = eps_n;
-        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+        lane.episode_end(tr, t);
+        lane.advance_schedules(eps_n);
     }
     if constexpr (RULE == TD_SARSA) pending[r] = act;
     for (int i = 0; i < L; ++i) {
@@ -187,15 +150,7 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvC
         w.r[(int64_t)i * c.M + r] = wr[k];
     }
     w.len[r] = L;
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 }  // namespace qe

@@ -70,81 +70,193 @@ struct RunsCtx {
     const unsigned long long* step_off;  // [M] per-run offsets added to step0 (NULL: every run draws at step0 + t)
 };
 
+// ---- what every population kernel shares ---------------------------------------------------------------------------
+// RunLane is the state one lane carries for its run through a launch, and the ONE copy of the protocol around a
+// kernel's own step.  k_rollout_runs and its siblings (qe_rollout_runs_td.h, _double.h, _nstep.h, _trace.h, _dyna.h,
+// _visit.h) build their steps from it; what it guarantees:
+//   construction   loads the per-run state of run r (the lane is inside the population: r < c.M).  SCHED = false (the
+//                  evaluation kernels) leaves c.eps / c.lr / c.gamma unread.
+//   draws          the Philox block of (agent_offset + r, step) of a stream; step counts from step0 = the launch's
+//                  step0 + the run's own offset (step_off), so a kernel's step t draws at step0 + t.
+//   settle         the empty-pick rule: a pick without a selectable action becomes action 0, which keeps the run inside
+//                  its table, and the run is flagged -- c.status[r] = 1 at the end of the launch, reported after the call.
+//   select, pick, pick_on_policy   the dispatcher's rule for one agent: explore when word 0 of the draws is below
+//                  eps_threshold(eps), words 1 and 2 choose the column (select_lane), the NaN rule on when the
+//                  population selects NumPy-style; then settle.
+//   episode_end    the running return takes the step's reward; a terminated step adds it to the float32 sequential
+//                  sum, counts the episode and clears it.  Its log entry is (c.t_call + t, return): the step within the
+//                  CALL.  A full segment skips the entry, the episode still counts.
+//   next_eps, advance_schedules   the schedules' own float64 operations, once per step.
+//   store          writes the state back.  c.seg_cnt[r] only with a log, c.status[r] only when flagged (the host
+//                  cleared it before the call).
+// The loads of the construction and the stores of store() keep the order they have here: the generated code is
+// sensitive to it.  Three kernels keep a line of their own where the shared form costs a build a wave per SIMD: the
+// evaluation kernels hold the flag of settle in a local (below), k_visit_rollout patches its two held rows in one
+// loop (qe_rollout_visit.h), and k_trace_rollout has its own copy of episode_end (qe_rollout_trace.h).
+template <typename T, int NV, bool MASKED, bool SCHED = true>
+struct RunLane {
+    const RunsCtx<T>& c;
+    const int64_t r;
+    int32_t n;     // observation
+    uint32_t aux;  // environment-internal word
+    float acc;     // running return
+    RunSched es, ls;
+    double eps_v, lr_v;
+    Hyper h;  // gamma here; the step sets its rate with learning_rate()
+    long long count;
+    float sum;
+    int32_t logged = 0;
+    bool empty = false;
+    bool nan_sel;
+    uint32_t id;  // the draw key of every rollout: the environment's agent id
+    unsigned long long step0;
+    long long seg0;  // the run's log segment starts here
+
+    __device__ __forceinline__ RunLane(const RunsCtx<T>& ctx, const EnvCtx& ev, int64_t run) : c(ctx), r(run) {
+        n = c.obs[r];
+        aux = c.aux[r];
+        acc = c.acc[r];
+        if constexpr (SCHED) {
+            es = c.eps[r]; ls = c.lr[r];
+            eps_v = es.value; lr_v = ls.value;
+            h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
+        }
+        count = c.ep_count[r];
+        sum = c.ep_sum[r];
+        nan_sel = c.nan_select != 0;
+        id = ev.agent_offset + (uint32_t)r;
+        step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+        seg0 = r * c.seg_len;
+    }
+
+    __device__ __forceinline__ U4 draws(unsigned long long step, uint32_t stream = STREAM_POLICY) const {
+        return philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), stream, c.seed_lo, c.seed_hi);
+    }
+
+    // the empty-pick rule: no selectable action (act < 0) becomes action 0, which keeps the run inside its table; true
+    // when it applied -- the run is then reported after the call
+    static __device__ __forceinline__ bool settle(int& act) {
+        if (act < 0) {
+            act = 0;
+            return true;
+        }
+        return false;
+    }
+
+    // the pick from a masked row with the draws x in hand; *value = the row's value of the returned action
+    template <typename M>
+    __device__ __forceinline__ int select(const RowV<T, NV>& rowm, M valid, bool explore, const U4& x, bool row_nan, T* value) {
+        int act = select_lane<T, NV, M>(rowm, valid, explore, x.y, x.z, value, nan_sel && row_nan);
+        empty |= settle(act);
+        return act;
+    }
+
+    // the epsilon-greedy pick from the row as loaded, with the draws of `step`
+    template <typename M>
+    __device__ __forceinline__ int pick(const RowV<T, NV>& row, M valid, bool row_nan, unsigned long long step, double eps, T* value) {
+        const U4 x = draws(step);
+        const bool explore = (unsigned long long)x.x < eps_threshold(eps);
+        return select(masked_row<MASKED>(row, valid), valid, explore, x, row_nan, value);
+    }
+
+    // ... of the on-policy kernels, whose *value is the next prediction: a flagged pick hands on row.v[0], the cell of
+    // action 0 itself, not its masked value
+    template <typename M>
+    __device__ __forceinline__ int pick_on_policy(const RowV<T, NV>& row, M valid, bool row_nan, unsigned long long step,
+                                                  double eps, T* value) {
+        const U4 x = draws(step);
+        const bool explore = (unsigned long long)x.x < eps_threshold(eps);
+        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, value, nan_sel && row_nan);
+        if (settle(act)) {
+            empty = true;
+            *value = row.v[0];
+        }
+        return act;
+    }
+
+    // the episode ends with step t of the launch
+    __device__ __forceinline__ void episode_done(long long t) {
+        if (logged < c.seg_len) {
+            const long long at = seg0 + logged;
+            c.seg_step[at] = (int32_t)(c.t_call + t);
+            c.seg_ret[at] = acc;
+            ++logged;
+        }
+        sum += acc;
+        ++count;
+        acc = 0.0f;
+    }
+    __device__ __forceinline__ void episode_end(const Transition& tr, long long t) {
+        acc += tr.reward;
+        if (tr.terminated) episode_done(t);
+    }
+
+    __device__ __forceinline__ void learning_rate(double lr) { h.lr = lr; h.lr32 = (float)lr; }
+    __device__ __forceinline__ double next_eps() const { return run_sched_next(eps_v, es.min_value, es.factor, es.kind); }
+    __device__ __forceinline__ void advance_schedules(double eps_next) {
+        eps_v = eps_next;
+        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+    }
+    __device__ __forceinline__ void advance_schedules() { advance_schedules(next_eps()); }
+
+    __device__ __forceinline__ void store() const {
+        c.obs[r] = n;
+        c.aux[r] = aux;
+        c.acc[r] = acc;
+        if constexpr (SCHED) {
+            c.eps[r].value = eps_v;
+            c.lr[r].value = lr_v;
+        }
+        c.ep_count[r] = count;
+        c.ep_sum[r] = sum;
+        if (c.seg_len) c.seg_cnt[r] = logged;
+        if (empty) c.status[r] = 1u;
+    }
+};
+
+// a store of q1 into column `act` of the row held in registers
+template <int NV, typename T>
+__device__ __forceinline__ void patch_own_write(RowV<T, NV>& row, int act, T q1) {
+#pragma unroll
+    for (int j = 0; j < 4 * NV; ++j) row.v[j] = j == act ? q1 : row.v[j];
+}
+
 template <typename T, class Env, int NV, bool MASKED>
 __global__ __launch_bounds__(RUNS_BLOCK) void k_rollout_runs(RunsCtx<T> c, EnvCtx ev, long long steps) {
     using M = typename LaneMask<NV>::type;
     const int64_t r = (int64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
     if (r >= c.M) return;
     T* const q = c.q + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;  // the draw key of every rollout: the environment's agent id
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps_v);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
         T picked;
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, &picked, nan_sel && row_nan);
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-        }
-        const int32_t s = n;
-        const Transition tr = Env::step(ev, r, s, aux, act, step);
-        n = tr.next_obs;
-        load_row_lane<NV>(row, q, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+        const int act = lane.pick(row, valid, row_nan, step, lane.eps_v, &picked);
+        const int32_t s = lane.n;
+        const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        load_row_lane<NV>(row, q, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
         const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
         row_nan = row_nan_lane<NV>(rowm);
         const T m = row_nan ? quiet_nan<T>() : row_max_lane(rowm);
-        h.lr = lr_v; h.lr32 = (float)lr_v;
+        lane.learning_rate(lane.lr_v);
         T u;
-        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, h, c.mode, &u);
+        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, lane.h, c.mode, &u);
         q[(int64_t)s * (4 * NV) + act] = q1;
-        if (n == s) {  // own write lands in the row held in registers
+        if (lane.n == s) {  // own write lands in the row held in registers
             row_nan |= q1 != q1;
-#pragma unroll
-            for (int j = 0; j < 4 * NV; ++j) row.v[j] = j == act ? q1 : row.v[j];
+            patch_own_write<NV>(row, act, q1);
         }
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-        eps_v = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
-        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+        lane.episode_end(tr, t);
+        lane.advance_schedules();
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 // Greedy evaluation of every run (qe_population_evaluate): run r is the standalone one-agent evaluate_steps /
@@ -166,59 +278,38 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_evaluate_runs(RunsCtx<T> c, EnvC
         return;
     }
     const T* const q = c.q + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
+    RunLane<T, NV, MASKED, false> lane(c, ev, r);
+    // (the flag of a pick without a selectable action stays a local here and goes to the lane before the store: as a
+    // member, written in a loop that a run can leave early, it costs the loop its scalar step counter and registers)
     bool empty = false, finished = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
 
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     long long t = 0;
     while (t < steps) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
+        const U4 x = lane.draws(step);
         const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
         T picked;
-        int act = select_lane<T, NV, M>(rowm, valid, false, x.y, x.z, &picked, nan_sel && row_nan_lane<NV>(rowm));
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-        }
-        const Transition tr = Env::step(ev, r, n, aux, act, step);
-        n = tr.next_obs;
-        acc += tr.reward;
+        int act = select_lane<T, NV, M>(rowm, valid, false, x.y, x.z, &picked, lane.nan_sel && row_nan_lane<NV>(rowm));
+        empty |= lane.settle(act);
+        const Transition tr = Env::step(ev, r, lane.n, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        lane.acc += tr.reward;
         ++t;
         if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t - 1);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-            if (episodes && count >= episodes) {
+            lane.episode_done(t - 1);
+            if (episodes && lane.count >= episodes) {
                 finished = true;
                 break;
             }
         }
-        load_row_lane<NV>(row, q, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+        load_row_lane<NV>(row, q, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.empty = empty;
+    lane.store();
     if (episodes) {
         used[r] += t;
         if (finished) done[r] = 1;

@@ -47,117 +47,66 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_rollout_runs_td(RunsCtx<T> c, En
     const int64_t r = (int64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;
     if (r >= c.M) return;
     T* const q = c.q + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
-
-    // the epsilon-greedy pick of the dispatcher's rule for one agent, with the draws of `step`; no selectable action:
-    // reported after the call, action 0 keeps the run inside its table
-    auto pick = [&](const RowV<T, NV>& row, M valid, bool row_nan, unsigned long long step, double eps, T* value) -> int {
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps);
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, value, nan_sel && row_nan);
-        if (act < 0) {
-            empty = true;
-            act = 0;
-            *value = row.v[0];
-        }
-        return act;
-    };
-    auto episode_end = [&](const Transition& tr, long long t) {
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-    };
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     if constexpr (RULE == TD_SARSA) {
         int act = pending[r];
         T picked;
-        if (act < 0) act = pick(row, valid, row_nan, step0, eps_v, &picked);
+        if (act < 0) act = lane.pick_on_policy(row, valid, row_nan, lane.step0, lane.eps_v, &picked);
         else picked = row_pick_lane(row, act);
         for (long long t = 0; t < steps; ++t) {
-            const unsigned long long step = step0 + (unsigned long long)t;
-            const int32_t s = n;
-            const Transition tr = Env::step(ev, r, s, aux, act, step);
-            n = tr.next_obs;
-            load_row_lane<NV>(row, q, n);
-            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+            const unsigned long long step = lane.step0 + (unsigned long long)t;
+            const int32_t s = lane.n;
+            const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+            lane.n = tr.next_obs;
+            load_row_lane<NV>(row, q, lane.n);
+            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
             row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
-            const double eps_n = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
+            const double eps_n = lane.next_eps();
             T v;
-            const int next = pick(row, valid, row_nan, step + 1ull, eps_n, &v);
-            h.lr = lr_v; h.lr32 = (float)lr_v;
+            const int next = lane.pick_on_policy(row, valid, row_nan, step + 1ull, eps_n, &v);
+            lane.learning_rate(lane.lr_v);
             T u;
-            const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, h, c.mode, &u);
+            const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, lane.h, c.mode, &u);
             q[(int64_t)s * (4 * NV) + act] = q1;
-            picked = (n == s && next == act) ? q1 : v;  // the next prediction is the cell as this step leaves it
+            picked = (lane.n == s && next == act) ? q1 : v;  // the next prediction is the cell as this step leaves it
             act = next;
-            episode_end(tr, t);
-            eps_v = eps_n;
-            lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+            lane.episode_end(tr, t);
+            lane.advance_schedules(eps_n);
         }
         pending[r] = act;
     } else {
         for (long long t = 0; t < steps; ++t) {
-            const unsigned long long step = step0 + (unsigned long long)t;
+            const unsigned long long step = lane.step0 + (unsigned long long)t;
             T picked;
-            const int act = pick(row, valid, row_nan, step, eps_v, &picked);
-            const int32_t s = n;
-            const Transition tr = Env::step(ev, r, s, aux, act, step);
-            n = tr.next_obs;
-            load_row_lane<NV>(row, q, n);
-            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+            const int act = lane.pick_on_policy(row, valid, row_nan, step, lane.eps_v, &picked);
+            const int32_t s = lane.n;
+            const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+            lane.n = tr.next_obs;
+            load_row_lane<NV>(row, q, lane.n);
+            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
             const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
             row_nan = row_nan_lane<NV>(rowm);
             const T m = row_nan ? quiet_nan<T>() : row_max_lane(rowm);
-            const double eps_n = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
+            const double eps_n = lane.next_eps();
             const T v = row_expected_lane<T, NV, M>(row, valid, m, eps_n);
-            h.lr = lr_v; h.lr32 = (float)lr_v;
+            lane.learning_rate(lane.lr_v);
             T u;
-            const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, h, c.mode, &u);
+            const T q1 = Td<T>::apply(picked, tr.reward, v, tr.terminated, lane.h, c.mode, &u);
             q[(int64_t)s * (4 * NV) + act] = q1;
-            if (n == s) {  // own write lands in the row held in registers
+            if (lane.n == s) {  // own write lands in the row held in registers
                 row_nan |= q1 != q1;
-#pragma unroll
-                for (int j = 0; j < 4 * NV; ++j) row.v[j] = j == act ? q1 : row.v[j];
+                patch_own_write<NV>(row, act, q1);
             }
-            episode_end(tr, t);
-            eps_v = eps_n;
-            lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+            lane.episode_end(tr, t);
+            lane.advance_schedules(eps_n);
         }
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 }  // namespace qe

@@ -71,23 +71,10 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_trace_rollout(RunsCtx<T> c, EnvC
     int32_t* const ws = reinterpret_cast<int32_t*>(reinterpret_cast<T*>(trace_lds) + K * RUNS_BLOCK) + threadIdx.x;
     int32_t* const wa = ws + K * RUNS_BLOCK;
     T* const q = c.q + r * c.S * (4 * NV);
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    const T decay = (T)(h.gamma * w.lambda[r]);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
+    const T decay = (T)(lane.h.gamma * w.lambda[r]);
     const bool accumulate = w.kind == TRACE_ACCUMULATING;
     const bool vec32 = F32 && c.mode == 1;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
 
     int hi = 0;  // one past the highest live slot: slots hi .. K-1 hold e == 0
     for (int i = 0; i < K; ++i) {
@@ -98,28 +85,19 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_trace_rollout(RunsCtx<T> c, EnvC
         if (e != T(0)) hi = i + 1;
     }
 
-    auto pick = [&](const RowV<T, NV>& row, M valid, bool row_nan, unsigned long long step, double eps, T* value) -> int {
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps);
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, value, nan_sel && row_nan);
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-            *value = row.v[0];
-        }
-        return act;
-    };
+    // RunLane::episode_end, kept here with the log index written out twice: with the shared form the double NV = 4 unmasked
+    // SARSA build needs 130 VGPRs, not 126, and loses a wave
     auto episode_end = [&](const Transition& tr, long long t) {
-        acc += tr.reward;
+        lane.acc += tr.reward;
         if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
+            if (lane.logged < c.seg_len) {
+                c.seg_step[r * c.seg_len + lane.logged] = (int32_t)(c.t_call + t);
+                c.seg_ret[r * c.seg_len + lane.logged] = lane.acc;
+                ++lane.logged;
             }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
+            lane.sum += lane.acc;
+            ++lane.count;
+            lane.acc = 0.0f;
         }
     };
     auto clear = [&]() {
@@ -190,83 +168,80 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_trace_rollout(RunsCtx<T> c, EnvC
     // step 4: the increment of Td<T>::apply
     auto increment = [&](T pred, float reward, T v, bool term, T* u, double* u64) {
         if constexpr (F32) {
-            if (c.mode == 0) (void)Td<float>::apply(pred, reward, v, term, h, 0, u);
-            else *u64 = Td<float>::vec_inc(pred, reward, v, term, h);
+            if (c.mode == 0) (void)Td<float>::apply(pred, reward, v, term, lane.h, 0, u);
+            else *u64 = Td<float>::vec_inc(pred, reward, v, term, lane.h);
         } else {
-            (void)Td<double>::apply(pred, reward, v, term, h, c.mode, u);
+            (void)Td<double>::apply(pred, reward, v, term, lane.h, c.mode, u);
         }
     };
 
     RowV<T, NV> row;
-    load_row_lane<NV>(row, q, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     bool row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
     if constexpr (RULE == TD_SARSA) {
         int act = pending[r];
         T picked;
-        if (act < 0) act = pick(row, valid, row_nan, step0, eps_v, &picked);
+        if (act < 0) act = lane.pick_on_policy(row, valid, row_nan, lane.step0, lane.eps_v, &picked);
         else picked = row_pick_lane(row, act);
         for (long long t = 0; t < steps; ++t) {
-            const unsigned long long step = step0 + (unsigned long long)t;
-            const int32_t s = n;
+            const unsigned long long step = lane.step0 + (unsigned long long)t;
+            const int32_t s = lane.n;
             const int mk = mark(s, act);
-            const Transition tr = Env::step(ev, r, s, aux, act, step);
-            n = tr.next_obs;
-            load_row_lane<NV>(row, q, n);
-            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+            const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+            lane.n = tr.next_obs;
+            load_row_lane<NV>(row, q, lane.n);
+            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
             row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
-            const double eps_n = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
+            const double eps_n = lane.next_eps();
             T v;
-            const int next = pick(row, valid, row_nan, step + 1ull, eps_n, &v);
-            h.lr = lr_v; h.lr32 = (float)lr_v;
+            const int next = lane.pick_on_policy(row, valid, row_nan, step + 1ull, eps_n, &v);
+            lane.learning_rate(lane.lr_v);
             T u = T(0);
             double u64 = 0.0;
             increment(picked, tr.reward, v, tr.terminated, &u, &u64);
             T carry = v;  // the next prediction is the cell as this step's sweep leaves it
             sweep(mk, picked, u, u64, tr.terminated, [&](int32_t si, int32_t ai, T qn) {
-                if (si == n && ai == next) carry = qn;
+                if (si == lane.n && ai == next) carry = qn;
             });
             picked = carry;
             act = next;
             episode_end(tr, t);
-            eps_v = eps_n;
-            lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+            lane.advance_schedules(eps_n);
         }
         pending[r] = act;
     } else {
         for (long long t = 0; t < steps; ++t) {
-            const unsigned long long step = step0 + (unsigned long long)t;
+            const unsigned long long step = lane.step0 + (unsigned long long)t;
             T picked;
-            const int act = pick(row, valid, row_nan, step, eps_v, &picked);
+            const int act = lane.pick_on_policy(row, valid, row_nan, step, lane.eps_v, &picked);
             {  // Watkins's cut: a non-greedy action ends every trace
                 const T top = row_nan ? quiet_nan<T>() : row_max_lane(masked_row<MASKED>(row, valid));
                 if (!(picked == top)) clear();
             }
-            const int32_t s = n;
+            const int32_t s = lane.n;
             const int mk = mark(s, act);
-            const Transition tr = Env::step(ev, r, s, aux, act, step);
-            n = tr.next_obs;
-            load_row_lane<NV>(row, q, n);
-            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+            const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+            lane.n = tr.next_obs;
+            load_row_lane<NV>(row, q, lane.n);
+            valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
             const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
             row_nan = row_nan_lane<NV>(rowm);
             const T m = row_nan ? quiet_nan<T>() : row_max_lane(rowm);
-            h.lr = lr_v; h.lr32 = (float)lr_v;
+            lane.learning_rate(lane.lr_v);
             T u = T(0);
             double u64 = 0.0;
             increment(picked, tr.reward, m, tr.terminated, &u, &u64);
             bool patched = false;
             sweep(mk, picked, u, u64, tr.terminated, [&](int32_t si, int32_t ai, T qn) {
-                if (si == n) {  // own write lands in the row held in registers
+                if (si == lane.n) {  // own write lands in the row held in registers
                     patched = true;
-#pragma unroll
-                    for (int x = 0; x < 4 * NV; ++x) row.v[x] = x == ai ? qn : row.v[x];
+                    patch_own_write<NV>(row, ai, qn);
                 }
             });
             if (patched) row_nan = row_nan_lane<NV>(masked_row<MASKED>(row, valid));
             episode_end(tr, t);
-            eps_v = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
-            lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+            lane.advance_schedules();
         }
     }
     for (int i = 0; i < K; ++i) {  // (slots from hi on: e == 0, written so; their s and a are not read by anyone)
@@ -274,15 +249,7 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_trace_rollout(RunsCtx<T> c, EnvC
         w.s[(int64_t)i * c.M + r] = ws[i * RUNS_BLOCK];
         w.a[(int64_t)i * c.M + r] = wa[i * RUNS_BLOCK];
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 }  // namespace qe

@@ -75,46 +75,29 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_visit_rollout(RunsCtx<T> c, EnvC
     T* const bon = (T*)w.b + r * c.S * LD;
     const double beta = w.beta[r];
     const bool visit_lr = w.visit_lr != 0;
-    int32_t n = c.obs[r];
-    uint32_t aux = c.aux[r];
-    float acc = c.acc[r];
-    const RunSched es = c.eps[r], ls = c.lr[r];
-    double eps_v = es.value, lr_v = ls.value;
-    Hyper h;
-    h.gamma = c.gamma[r]; h.gamma32 = (float)h.gamma;
-    long long count = c.ep_count[r];
-    float sum = c.ep_sum[r];
-    int32_t logged = 0;
-    bool empty = false;
-    const bool nan_sel = c.nan_select != 0;
-    const uint32_t id = ev.agent_offset + (uint32_t)r;
-    const unsigned long long step0 = c.step0 + (c.step_off ? c.step_off[r] : 0ull);
+    RunLane<T, NV, MASKED> lane(c, ev, r);
 
     RowV<T, NV> row, brow;
-    load_row_lane<NV>(row, q, n);
-    load_row_lane<NV>(brow, bon, n);
-    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+    load_row_lane<NV>(row, q, lane.n);
+    load_row_lane<NV>(brow, bon, lane.n);
+    M valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
     for (long long t = 0; t < steps; ++t) {
-        const unsigned long long step = step0 + (unsigned long long)t;
-        const U4 x = philox4x32_10(id, (uint32_t)step, (uint32_t)(step >> 32), STREAM_POLICY, c.seed_lo, c.seed_hi);
-        const bool explore = (unsigned long long)x.x < eps_threshold(eps_v);
+        const unsigned long long step = lane.step0 + (unsigned long long)t;
+        const U4 x = lane.draws(step);
+        const bool explore = (unsigned long long)x.x < eps_threshold(lane.eps_v);
         // 1. the pick sees the score row; the update's prediction is the table's own value
         const RowV<T, NV> score = masked_row<MASKED>(visit_score<T, NV>(row, brow), valid);
         T scored;
-        int act = select_lane<T, NV, M>(score, valid, explore, x.y, x.z, &scored, nan_sel && row_nan_lane<NV>(score));
-        if (act < 0) {  // no selectable action: reported after the call, action 0 keeps the run inside its table
-            empty = true;
-            act = 0;
-        }
+        const int act = lane.select(score, valid, explore, x, row_nan_lane<NV>(score), &scored);
         const T picked = row_pick_lane(masked_row<MASKED>(row, valid), act);
-        const int32_t s = n;
+        const int32_t s = lane.n;
         const int64_t cell = (int64_t)s * LD + act;
         const uint32_t seen = cnt[cell];  // (in flight beside the environment step and the gather)
-        const Transition tr = Env::step(ev, r, s, aux, act, step);
-        n = tr.next_obs;
-        load_row_lane<NV>(row, q, n);
-        load_row_lane<NV>(brow, bon, n);
-        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, n);
+        const Transition tr = Env::step(ev, r, s, lane.aux, act, step);
+        lane.n = tr.next_obs;
+        load_row_lane<NV>(row, q, lane.n);
+        load_row_lane<NV>(brow, bon, lane.n);
+        valid = valid_mask_lane<Env, NV, MASKED>(ev, r, lane.n);
         const RowV<T, NV> rowm = masked_row<MASKED>(row, valid);
         const T m = row_nan_lane<NV>(rowm) ? quiet_nan<T>() : row_max_lane(rowm);
         // 2. the count, and the one cell of the bonus plane that follows it
@@ -123,41 +106,22 @@ __global__ __launch_bounds__(RUNS_BLOCK) void k_visit_rollout(RunsCtx<T> c, EnvC
         cnt[cell] = visits;
         bon[cell] = b1;
         // 3. the rate
-        const double alpha = visit_lr ? lr_v / (double)visits : lr_v;
-        h.lr = alpha; h.lr32 = (float)alpha;
+        const double alpha = visit_lr ? lane.lr_v / (double)visits : lane.lr_v;
+        lane.learning_rate(alpha);
         T u;
-        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, h, c.mode, &u);
+        const T q1 = Td<T>::apply(picked, tr.reward, m, tr.terminated, lane.h, c.mode, &u);
         q[cell] = q1;
-        if (n == s) {  // own writes land in the rows held in registers
+        if (lane.n == s) {  // own writes land in the rows held in registers
 #pragma unroll
             for (int j = 0; j < LD; ++j) {
                 row.v[j] = j == act ? q1 : row.v[j];
                 brow.v[j] = j == act ? b1 : brow.v[j];
             }
         }
-        acc += tr.reward;
-        if (tr.terminated) {
-            if (logged < c.seg_len) {
-                c.seg_step[r * c.seg_len + logged] = (int32_t)(c.t_call + t);
-                c.seg_ret[r * c.seg_len + logged] = acc;
-                ++logged;
-            }
-            sum += acc;
-            ++count;
-            acc = 0.0f;
-        }
-        eps_v = run_sched_next(eps_v, es.min_value, es.factor, es.kind);
-        lr_v = run_sched_next(lr_v, ls.min_value, ls.factor, ls.kind);
+        lane.episode_end(tr, t);
+        lane.advance_schedules();
     }
-    c.obs[r] = n;
-    c.aux[r] = aux;
-    c.acc[r] = acc;
-    c.eps[r].value = eps_v;
-    c.lr[r].value = lr_v;
-    c.ep_count[r] = count;
-    c.ep_sum[r] = sum;
-    if (c.seg_len) c.seg_cnt[r] = logged;
-    if (empty) c.status[r] = 1u;
+    lane.store();
 }
 
 }  // namespace qe

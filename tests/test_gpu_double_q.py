@@ -340,6 +340,97 @@ def test_step_and_episode_evaluation_match_the_model(dt):
         _check(pop, more, r, run, history, at, ta, tb, run.rt.step_counter)
 
 
+def _flag_empty_picks(rt):
+    """The oracle's greedy evaluation hands the list selection's -1 (no selectable action) on to the environment; every
+    engine path raises IndexError for such a run, as the model's training steps do.  The same for the evaluation's picks."""
+    greedy = rt._greedy
+
+    def pick(states):
+        actions = greedy(states)
+        if actions[0] < 0:
+            msg = "Cannot choose from an empty sequence"
+            raise IndexError(msg)
+        return actions
+
+    rt._greedy = pick
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_an_evaluation_that_meets_an_all_invalid_mask_row_names_its_runs_and_the_others_match(dt):
+    """k_double_evaluate's empty pick: the runs whose greedy walk reaches the dead state are named, exactly the model's,
+    and every other run's returns are the model's."""
+    M, V = M_ODD, 12
+    sched = _schedules(M)
+    p = {"mdp": dead_row_mdp(), "seed": 3}
+    rng = np.random.default_rng(5)
+    qa0, qb0 = (rng.standard_normal((M, 20, 5)).astype(dt) for _ in range(2))
+    pop = _population(M, 20, 5, sched, 6, dt, "iter")
+    pop.set_q_tables(qa0, qb0)
+    try:
+        res, raised = pop.evaluate_steps(_device_env("table", M, p), V), []
+    except IndexError as err:
+        assert str(err).startswith("Cannot choose from an empty sequence (runs ")
+        res, raised = err.result, err.runs
+    _reached(pop, "population_double_eval", nv=2, masked=True)
+    done, flagged = {}, []
+    for r, run in _model_runs("table", p, range(M), sched, 6, dt, "iter", qa0, qb0).items():
+        _flag_empty_picks(run.rt)
+        try:
+            done[r] = run.evaluate_steps(_model_env("table", r, p), V)
+        except IndexError:
+            flagged.append(r)
+    assert raised == flagged and flagged, "no run met the row without a selectable action"
+    assert len(done) >= (M + 1) // 2, "the case must keep at least half its runs"
+    for r, (total, history) in done.items():
+        assert np.array_equal(res.run_returns(r), np.array(history, dtype=np.float32)), f"run {r}: returns"
+        assert res.totals[r] == np.float32(total) and res.episode_counts[r] == len(history), r
+
+
+@pytest.mark.parametrize("mode", ["steps", "episodes"])
+def test_a_logged_evaluation_cut_into_launches_equals_the_unlogged_one_and_the_model(mode):
+    """k_double_evaluate over several launches with the log: 20 000 runs leave a logged launch 2**23 // 20 000 = 419
+    steps, and on this MDP (one outcome in three of every move is terminal) every run ends episodes in each of them."""
+    from test_gpu_population_eval import _slippery_mdp
+
+    envs, sch = _product()[1:3]
+    M = 20_000
+    mdp = _slippery_mdp(envs, seed=21, S=24, A=8)
+    S, A = mdp.state_size, mdp.action_size
+    rng = np.random.default_rng(0)
+    qa0, qb0 = (rng.normal(size=(M, S, A)).astype(np.float32) for _ in range(2))
+    sched = ([sch.ConstantSchedule(0.1)] * M, [sch.ConstantSchedule(0.1)] * M, [0.9] * M)
+    pop = _population(M, S, A, sched, 1, np.float32, "iter")
+    pop.set_q_tables(qa0, qb0)
+    if mode == "steps":
+        V = 900  # two launches of 419 steps and one of 62
+        res = pop.evaluate_steps(envs.TabularMDPEnv(M, mdp, seed=6), V)
+        assert pop.last_stats["launches"] == 3 * 3  # each launch with its log scan and pack
+        pop.step_counter = 0  # the same evaluation again, without the log
+        plain = pop.evaluate_steps(envs.TabularMDPEnv(M, mdp, seed=6), V, log=False)
+        assert pop.last_stats["launches"] == 1
+    else:
+        E = 150  # about 900 steps per run
+        res = pop.evaluate_episodes(envs.TabularMDPEnv(M, mdp, seed=6), E)
+        assert res.finished.all() and res.steps_used.min() > 419
+        assert pop.last_stats["launches"] >= 3 * 3
+        pop.step_counter = 0
+        plain = pop.evaluate_episodes(envs.TabularMDPEnv(M, mdp, seed=6), E, log=False)
+    _reached(pop, "population_double_eval", nv=2, masked=False)
+    assert np.array_equal(plain.totals, res.totals) and np.array_equal(plain.steps_used, res.steps_used)
+    assert np.array_equal(plain.episode_counts, res.episode_counts)
+    assert np.array_equal(np.diff(res.offsets), res.episode_counts)
+    picked = [0, 1, 63, 64, 10_000, M - 1]
+    for r, run in _model_runs("table", {"mdp": mdp, "seed": 6}, picked, sched, 1, np.float32, "iter", qa0, qb0).items():
+        env = TableMDPVecEnv(1, mdp, seed=6, agent_offset=r)
+        if mode == "steps":
+            total, history = run.evaluate_steps(env, V)
+        else:
+            total, history = run.evaluate_episodes(env, E)
+            assert res.steps_used[r] == run.rt.step_counter, r
+        assert len(history) > 2 and np.array_equal(res.run_returns(r), np.array(history, dtype=np.float32)), r
+        assert res.totals[r] == np.float32(total) and res.episode_counts[r] == len(history), r
+
+
 def test_train_with_episode_validation_matches_the_model_driven_the_same_way():
     from test_gpu_population_eval import _slippery_mdp
 
