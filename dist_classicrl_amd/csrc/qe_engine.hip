@@ -387,10 +387,9 @@ int rollout_begin(qe_engine* e, qe_env* env, RolloutSlot& sl, RolloutPath path, 
     ReplayDev rp{};
     if (e->replay && learn) {  // device-to-device push of every transition (experience_replay.py:68-86)
         qe_replay* rb = e->replay;
-        rp = ReplayDev{rb->s.p, rb->a.p, rb->n.p, rb->r.p, rb->d.p, (long long)rb->capacity, (long long)rb->position};
-        const int64_t pushed = steps * env->N;
-        if (rb->position + pushed >= rb->capacity) rb->full = true;  // :85-86
-        rb->position = (rb->position + pushed) % rb->capacity;
+        // only the last `capacity` pushes of the rollout are stored: one store per slot (ReplayDev)
+        const long long first = std::max<long long>(0, (long long)(steps * env->N) - (long long)rb->capacity);
+        rp = ReplayDev{rb->s.p, rb->a.p, rb->n.p, rb->r.p, rb->d.p, (long long)rb->capacity, (long long)rb->position, first};
     }
     if (learn && e->opt_path == 2 && path != RolloutPath::Persistent)
         return qe_fail(QE_ERR_UNSUPPORTED, "persistent rollout needs num_agents <= 512 and action_size <= 64 (have %lld agents, %d actions)",
@@ -446,6 +445,12 @@ int rollout_begin(qe_engine* e, qe_env* env, RolloutSlot& sl, RolloutPath path, 
     if (e->dlog && learn)  // the steps whose records all fit
         e->dlog_count += std::min<long long>(steps, (e->dlog_cap - e->dlog_count) / env->N) * env->N;
     e->step_ctr += (uint64_t)steps;
+    if (rp.s) {  // the rollout is enqueued: only now does the ring move (a refused call leaves it as it was)
+        qe_replay* rb = e->replay;
+        const int64_t pushed = steps * env->N;
+        if (rb->position + pushed >= rb->capacity) rb->full = true;  // :85-86
+        rb->position = (rb->position + pushed) % rb->capacity;
+    }
     sl.busy = true;
     return QE_OK;
 }

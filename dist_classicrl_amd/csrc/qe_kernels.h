@@ -72,14 +72,18 @@ struct DeltaEntry {
 
 // Experience-replay ring attached to the fused rollout (algorithms/buffers/experience_replay.py:68-86:
 // every transition is pushed, here device to device): entry of agent i at vector step t goes to slot
-// (pos0 + t * N + i) mod cap -- the order in which a host loop would push them.
+// (pos0 + t * N + i) mod cap -- the order in which a host loop would push them.  A rollout of more than `cap`
+// pushes stores only its last `cap` (in-rollout index t * N + i >= first): those land in distinct slots, so every
+// slot is written at most once per rollout and no two agents ever race for one (with cap < N, agents i and i + cap
+// of ONE step share a slot, and the five stores of two lanes, wavefronts or workgroups could interleave).  Rollouts
+// are stream-ordered, so a later one still overwrites an earlier one like the host loop would.
 struct ReplayDev {
     int64_t* s;   // nullptr: no ring attached
     int64_t* a;
     int64_t* n;
     double* r;
     uint8_t* d;
-    long long cap, pos0;
+    long long cap, pos0, first;
 };
 
 // Result block of one rollout in page-locked, host-coherent memory.  The LAST kernel of a rollout
@@ -249,7 +253,9 @@ template <typename T>
 __device__ __forceinline__ void replay_put(const Ctx<T>& c, long long t, int64_t i, int32_t s, int32_t a, float r,
                                            int32_t n, bool term) {
     if (c.rp.s) {
-        const long long slot = (c.rp.pos0 + t * c.N + i) % c.rp.cap;
+        const long long g = t * c.N + i;
+        if (g < c.rp.first) return;  // overwritten later in this rollout: never stored (see ReplayDev)
+        const long long slot = (c.rp.pos0 + g) % c.rp.cap;
         c.rp.s[slot] = s; c.rp.a[slot] = a; c.rp.r[slot] = (double)r; c.rp.n[slot] = n; c.rp.d[slot] = term ? 1 : 0;
     }
 }

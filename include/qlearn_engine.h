@@ -564,7 +564,11 @@ int qe_replay_push(qe_replay* rb, const int64_t* states, const int64_t* actions,
 /* Wire the ring to the fused rollout: from now on every transition (s, a, r, s', done) of every agent and
  * vector step of qe_rollout / qe_rollout_begin / qe_rollout_fused on this engine is pushed device to device,
  * in (step, agent) order -- what a host loop calling push after every env.step would store (:68-86);
- * position / full advance accordingly.  rb == NULL detaches. */
+ * position / full advance accordingly -- once the rollout is enqueued: a call that is refused (e.g.
+ * QE_ERR_UNSUPPORTED for a forced path that does not fit) leaves position, full and the entries as they were.
+ * A rollout that pushes more than `capacity` entries stores only its last `capacity`: every slot is written
+ * at most once per rollout, so a ring smaller than one vector step (capacity < num_agents) also ends with
+ * whole entries, those of the latest pushes.  rb == NULL detaches. */
 int qe_replay_attach(qe_engine* e, qe_replay* rb);
 int64_t qe_replay_len(qe_replay* rb);
 int64_t qe_replay_position(qe_replay* rb);

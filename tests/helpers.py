@@ -221,6 +221,79 @@ def shares_a_cell_within_a_step(cells, n):
     return bool((by_step[:, 1:] == by_step[:, :-1]).any())
 
 
+# ------------------------------------------------------------------------------- the replay ring fed by the closed loop
+def run_oracle_transitions(env, chunks, dt, sched, learn_mode, gamma=0.99, seed=0):
+    """The closed loop of ``OracleRuntime`` on `env` in `chunks` consecutive run_steps-sized pieces, plus what a host loop
+    calling ``ExperienceReplay.push`` after every ``env.step`` would push: ``(s, a, r, s', terminated)`` of every agent
+    and step in (step, agent) order.  ``OracleRuntime._learn`` is wrapped and the records are its arguments: `s` and
+    `s'` are the ``"observation"`` entries of a masked environment, `done` is ``terminateds`` (not ``truncateds``).
+
+    Returns ``{"s", "a", "r", "s2", "d"}`` (int64, int64, float32, int64, bool; steps * agents entries each), ``"n"``
+    (agents) and ``"chunks"``: per chunk the table, the history so far, the observations, the running returns and the
+    number of vector steps (``"steps"``) at its end."""
+    algo = OracleQLearning(env.state_size, env.action_size, gamma, seed=seed, dtype=np.dtype(dt))
+    lr_p, eps_p = schedule_params(sched)
+    rt = OracleRuntime(algo, OracleSchedule(*lr_p), OracleSchedule(*eps_p), learn_mode=learn_mode)
+    rec = {k: [] for k in ("s", "a", "r", "s2", "d")}
+    inner = rt._learn
+
+    def learn(states, actions, rewards, next_states, terminateds):
+        masked = isinstance(next_states, dict)
+        rec["s"].append(np.array(states["observation"] if masked else states, dtype=np.int64))
+        rec["a"].append(np.array(actions, dtype=np.int64))
+        rec["r"].append(np.array(rewards, dtype=np.float32))
+        rec["s2"].append(np.array(next_states["observation"] if masked else next_states, dtype=np.int64))
+        rec["d"].append(np.array(terminateds, dtype=bool))
+        inner(states, actions, rewards, next_states, terminateds)
+
+    rt._learn = learn
+    states, _ = env.reset()
+    acc = np.zeros(env.num_agents, dtype=np.float32)
+    history, out, done = [], [], 0
+    for k in chunks:
+        for _ in range(k):
+            states, _ = rt.run_single_step(env, states, acc, history)
+        done += k
+        obs = states["observation"] if isinstance(states, dict) else states
+        out.append({"q": algo.q_table.copy(), "history": np.array(history, dtype=np.float32),
+                    "final_obs": np.asarray(obs, dtype=np.int32).copy(), "agent_rewards": acc.copy(), "steps": done})
+    res = {k: np.concatenate(v) for k, v in rec.items()}
+    res.update(n=env.num_agents, chunks=out)
+    return res
+
+
+def ring_after(transitions, capacity, position0=0, full0=False):
+    """The ring a host loop leaves that pushes `transitions` (``(s, a, r, s', d)``, five equally long arrays) one entry
+    at a time into an ``ExperienceReplay`` of `capacity` slots standing at `position0` / `full0`: push k goes to slot
+    ``(position0 + k) % capacity``, and a slot holds the entry of the LARGEST push index that maps to it.
+
+    Returns the five buffers (the reference's dtypes; slots these pushes did not write hold zero), ``position``,
+    ``full``, ``len`` and ``written``: bool[capacity], the slots these pushes wrote."""
+    s, a, r, s2, d = (np.asarray(x) for x in transitions)
+    k = len(s)
+    assert len(a) == len(r) == len(s2) == len(d) == k and 0 <= position0 < capacity
+    out = {"state": np.zeros(capacity, dtype=np.int64), "action": np.zeros(capacity, dtype=np.int64),
+           "reward": np.zeros(capacity, dtype=np.float64), "next_state": np.zeros(capacity, dtype=np.int64),
+           "done": np.zeros(capacity, dtype=bool), "written": np.zeros(capacity, dtype=bool)}
+    push = np.arange(max(0, k - capacity), k)  # the last `capacity` pushes: one per slot, nothing overwrites them
+    slot = (position0 + push) % capacity
+    assert len(np.unique(slot)) == len(slot)
+    for name, src in (("state", s), ("action", a), ("reward", r), ("next_state", s2), ("done", d)):
+        out[name][slot] = src[push]
+    out["written"][slot] = True
+    out["position"] = (position0 + k) % capacity
+    out["full"] = bool(full0 or position0 + k >= capacity)
+    out["len"] = capacity if out["full"] else out["position"]
+    return out
+
+
+def transitions_of(want, first_step=0, last_step=None):
+    """The five arrays of ``run_oracle_transitions``' result, vector steps [first_step, last_step)."""
+    n = want["n"]
+    lo, hi = first_step * n, None if last_step is None else last_step * n
+    return tuple(want[k][lo:hi] for k in ("s", "a", "r", "s2", "d"))
+
+
 # ------------------------------------------------------------------------------- tables too large for the host
 def lazy_zero_table(S, A, dtype):
     """An all-zero (S, A) table that costs memory only where it is touched: an anonymous private mapping (zero pages on
