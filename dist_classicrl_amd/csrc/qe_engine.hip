@@ -308,11 +308,21 @@ int wide_setup(qe_engine* e, RolloutSlot& sl) {
     return QE_OK;
 }
 
+// The result blocks belong to the engine's slots, not to an environment: before a slot's block takes the state of the
+// next rollout (or is freed), every environment of the engine that still serves observe / aux from it (mirror_*, set
+// when its own rollout finished in that slot) goes back to reading the device, whose copy of its state nothing touched.
+static void drop_mirrors(qe_engine* e, const RolloutSlot& sl) {
+    if (!sl.hb_obs) return;
+    for (qe_env* each : e->envs)
+        if (each->mirror_obs == sl.hb_obs) { each->mirror_obs = nullptr; each->mirror_aux = nullptr; each->mirror_acc = nullptr; }
+}
+
 // Persistent path: the kernel publishes its results itself into page-locked, host-coherent memory (host result
 // block) sized for the environment's agents.  Both slots' blocks at once: a later, longer call that pipelines through
 // the other slot finds it ready.
 int host_block_setup(qe_engine* e, qe_env* env, RolloutSlot& sl) {
     const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
+    drop_mirrors(e, sl);
     for (RolloutSlot& each : e->slots) {
         if (!each.hb) {
             HIP_TRY(hipHostMalloc((void**)&each.hb, sizeof(HostBlock), flags));
@@ -321,6 +331,7 @@ int host_block_setup(qe_engine* e, qe_env* env, RolloutSlot& sl) {
             HIP_TRY(hipHostMalloc((void**)&each.hb_ret, (size_t)HOST_LOG_CAP * sizeof(float), flags));
         }
         if ((size_t)env->N > each.hb_agents) {
+            drop_mirrors(e, each);
             for (void* h : {(void*)each.hb_obs, (void*)each.hb_aux, (void*)each.hb_acc})
                 if (h) (void)hipHostFree(h);
             each.hb_obs = nullptr; each.hb_aux = nullptr; each.hb_acc = nullptr; each.hb_agents = 0;
