@@ -18,6 +18,34 @@
 //     path of qe_kernels.h, which brings its own lane-group view of the rows) otherwise; an agent whose
 //     next-state row is written by someone else selects after all updates of the step.
 // learn_vec (np.add.at order) takes the same route with the batch path of slow_body.
+//
+// SLIM (the sparse builds: HELP, FULL, SEQ and LEAN 1 / 2 -- the builds the headline shape and its replica form run).
+// A wavefront that is alone on its SIMD issues one instruction per >= 4 cycles whatever its type, so every instruction
+// on the agents' wavefronts costs ~2 ns of every step and an instruction on a helper wavefront costs nothing.  Three
+// sections of the quiet step that do not feed the chain env.step -> next gather are therefore off the agents'
+// wavefronts in these builds (every other instantiation compiles to the code it had without them):
+//   * predicted value.  p.pred = Q[s, a] at selection time is first used by the update of the NEXT step.  It is not
+//     picked out of the row in registers (row_pick_lane: 53 instructions); one scalar-per-lane load of the cell is
+//     issued right behind the row gather and taken over at the top of the next step, so NLOAD + 1 loads stay in flight
+//     across the step barrier.  The cell's address is kept for that step's store.  Exact, because the cell can change
+//     between this selection and this agent's next update only through a write into row s, and
+//       - a write by another agent in the current step makes this step busy (W-R): its selections run after all
+//         updates and their barriers, and the load is issued after them;
+//       - a write by another agent in the next step makes that step busy (W-W): the later touchers re-read q0 from
+//         the table there, and the lowest toucher goes first with its carried value;
+//       - the agent's own store of this step (n == s and the same column picked again) is an earlier access of the
+//         same lane to the same address.
+//   * episode accounting.  Helper lane ii already produces the draws of agent ii; it also keeps that agent's running
+//     return and writes the episode log.  The agents' wavefront hands {reward, terminated} of the transition it just
+//     selected over with one LDS store behind the row gather (a two-slot ring by step parity, like the draws); the
+//     step barrier publishes it and the helper accounts it at the top of the step that updates the transition -- the
+//     step in which the agents' wavefront did it before, so keys, flush windows and log positions are what they were.
+//     Helpers read c.acc at the start and write acc / hb_acc at the end.
+//   * schedule values.  The helper lane that writes the draws of step t + 2 also loads lr[t + 1] and thr[t + 2]
+//     (scalar loads, clamped at the call's end) into the ring slot; the agents read both with the draws (one address
+//     for all lanes: a broadcast).  No vector loads, 64-bit address arithmetic or take-over moves on the agents' side.
+// (Measured and left out: handing the update's row maximum to the selection, recomputed only where the own write
+// landed in the row -- eight v_max3 fewer in the quiet step, but 0.015 us per step SLOWER on the benchmark.)
 #pragma once
 #include "qe_kernels.h"
 
@@ -175,7 +203,9 @@ __device__ __forceinline__ int kth_set_bit(M f, int k) {
 // valid maximum, k = mulhi(x2, n_ties).  Returns -1 when no action is selectable.  `rowm` = masked_row.
 // `nan_max`: some valid column holds a NaN AND the selection follows a NumPy variant of the reference (see
 // select_action): the maximum is NaN, nothing ties with it.
-template <typename T, int NV, typename M>
+// PICK = false: the caller does not want the picked value (`picked` is left alone; the sparse builds read the
+// cell from the table instead, see k_rollout_lane).
+template <typename T, int NV, typename M, bool PICK = true>
 __device__ __forceinline__ int select_lane(const RowV<T, NV>& rowm, M valid, bool explore, uint32_t x1,
                                            uint32_t x2, T* picked, bool nan_max) {
     T m = row_max_lane(rowm);
@@ -187,7 +217,7 @@ __device__ __forceinline__ int select_lane(const RowV<T, NV>& rowm, M valid, boo
     const int total = popc_mask(f);
     int act = -1;
     if (total > 0) act = kth_set_bit<NV>(f, (int)mulhi32(explore ? x1 : x2, (uint32_t)total));
-    *picked = row_pick_lane(rowm, act < 0 ? 0 : act);  // a selectable column is valid: rowm holds its Q-value
+    if constexpr (PICK) *picked = row_pick_lane(rowm, act < 0 ? 0 : act);  // a selectable column is valid: rowm holds its Q-value
     return act;
 }
 
@@ -247,6 +277,30 @@ struct LaneLds {
     int seq_min[2];       // SEQ builds: lowest pending agent of the current / the next round of a complex step
 };
 
+// SLIM builds (see k_rollout_lane): the helpers' ring carries, next to the draws of a step, the schedule values
+// that step reads.  Appended behind the common members, whose offsets stay what they are in every other build.
+struct alignas(16) SchedSlot {
+    double lr;               // lr[t1 - 1]: the learning rate of the update that runs in the step selecting t1
+    unsigned long long thr;  // thr[t1] (the call's last entry beyond its end)
+};
+template <int CAP>
+struct LaneLdsSlim : LaneLds<CAP, true> {
+    SchedSlot sched[2];  // by step parity, like draws
+    uint2 acct[2][CAP];  // {reward bits, terminated} of transition t per agent (parity of t): agents -> helpers
+};
+
+// a copy the optimiser cannot see through (take-over of a value loaded one step ahead, see the step loop)
+__device__ __forceinline__ float opaque_copy(float v) {
+    float r;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
+__device__ __forceinline__ double opaque_copy(double v) {
+    double r;
+    asm volatile("v_mov_b64 %0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
+
 #ifdef QE_EXPERIMENT
 #define QX(bit) ((flags >> (20 + (bit))) & 1)
 #else
@@ -286,7 +340,8 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
     using M = typename LaneMask<NV>::type;
     constexpr int NLOAD = NV * (int)(sizeof(T) / 4);  // 16-byte loads of one row gather
     constexpr int WT = LaneCfg<CAP>::WT, BT = LaneCfg<CAP>::BT;
-    __shared__ LaneLds<CAP, HELP> lds;
+    constexpr bool SLIM = HELP && SEQ && FULL && LEAN != 0;  // the sparse builds, see the header comment
+    __shared__ std::conditional_t<SLIM, LaneLdsSlim<CAP>, LaneLds<CAP, HELP>> lds;
     const unsigned long long clk0 = wall_clock64();
     const unsigned long long cyc0 = __builtin_amdgcn_s_memtime();
     if (c.thr == nullptr) {  // short rollout: the schedule values came with the launch
@@ -344,10 +399,11 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
     // selection + env.step of step t1 from `row` (= Q[p.n]); the new pending transition replaces p
     // (`row_nan`: the masked row holds a NaN -- handed in because the quiet path knows it from its update)
     const bool nan_sel = c.nan_select != 0;
+    // (SLIM builds: p.pred is not produced here -- it is read from the table behind the next row gather)
     auto advance = [&](const RowV<T, NV>& row, M valid, long long t1, const U4& x, unsigned long long thr_t1, bool row_nan) {
         const bool explore = (unsigned long long)x.x < thr_t1;
-        T picked;
-        int act = select_lane<T, NV, M>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, &picked, nan_sel && row_nan);
+        T picked = p.pred;
+        int act = select_lane<T, NV, M, !SLIM>(masked_row<MASKED>(row, valid), valid, explore, x.y, x.z, &picked, nan_sel && row_nan);
         if (act < 0) {
             // no selectable action (everything masked, or a NaN row maximum): the reference's
             // random.choice raises IndexError (q_learning_optimal.py:470,563); reported at the end of the
@@ -379,6 +435,49 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
         const U4 x = philox_of(t1);
         const int slot = (int)(t1 & 1);
         lds.draws[slot][0][ii] = x.x; lds.draws[slot][1][ii] = x.y; lds.draws[slot][2][ii] = x.z;
+        if constexpr (SLIM) {
+            // ... and the schedule values the agents read in the step that selects t1 (uniform scalar loads, from the
+            // uploaded plan or the kernel-argument segment alike; indices clamped at the call's end)
+            if (tid == n_main) {
+                lds.sched[slot].lr = c.lr[t1 - 1];
+                lds.sched[slot].thr = c.thr[t1 < steps ? t1 : (steps > 0 ? steps - 1 : 0)];
+            }
+        }
+    };
+    // SLIM builds, helper wavefronts: base_runtime.py:212,218-221 for transition tk of agent ii, from the {reward,
+    // terminated} pair its owner left in the ring (published by a barrier since).  An episode that ends is staged in
+    // LDS (flushed in bulk): one returning LDS atomic per wavefront reserves the slots of all its lanes; entry k of a
+    // flush window lands at log position ep_base + k.  Runs at the top of step tk, off the agents' wavefronts.
+    auto helper_account = [&](long long tk) {
+        if constexpr (SLIM) {
+            const uint2 rt = lds.acct[tk & 1][ii];
+            const bool term = rt.y != 0u;
+            acc += __uint_as_float(rt.x);
+            const bool ends = term && (flags & FLAG_ACCOUNT);
+            const unsigned long long enders = __ballot(ends);
+            const float ep_value = acc;
+            if (term) acc = 0.0f;
+            if (enders) {
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(enders >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)enders, 0u));
+                unsigned ep_raw = 0;
+                if (ends && rank == 0) ep_raw = atomicAdd(&lds.ep_n, (unsigned)__popcll(enders));  // the first ending lane
+                const unsigned base = __builtin_amdgcn_readlane(ep_raw, __ffsll((long long)enders) - 1);
+                if (ends) {
+                    const unsigned ep_slot = base + rank;
+                    const unsigned long long key = ((unsigned long long)tk << 32) | (unsigned long long)ii;
+                    if (ep_slot < (unsigned)EP_STAGE) {
+                        lds.ep_key[ep_slot] = key;
+                        lds.ep_ret[ep_slot] = ep_value;
+                    } else {  // more episodes end in one window than the stage holds: straight to memory
+                        const Ctx<T>& cc = *reinterpret_cast<const Ctx<T>*>(lds.cold);
+                        if ((long long)(ep_base + ep_slot) < cc.ep_cap) {
+                            cc.ep_key[ep_base + ep_slot] = key;
+                            cc.ep_ret[ep_base + ep_slot] = ep_value;
+                        }
+                    }
+                }
+            }
+        }
     };
     // The contention bookkeeping of the transition pending in p (step k): see the top of this section.
     // Returns whether the gathered row of p.n may be stale.  The three operations share the hash of p.n and
@@ -415,6 +514,10 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
 
     RowV<T, NV> row;   // Q[p.n] of the step about to be processed: gathered before its barrier
     bool stale = false;  // ... unless someone wrote that row in the step before: gathered again after it
+    // SLIM builds: the cell Q[p.s, p.a] of the pending transition and its value, loaded behind the row gather and taken
+    // over into p.pred at the top of the step that updates it (header comment: "predicted value")
+    T* pred_cell = c.q;
+    T pred_pend = 0;
     {   // select(0), env.step(0); rows written in step 0; then the bookkeeping of transition 0
         load_row_lane<NV>(row, c.q, p.n);
         if (active) {
@@ -433,27 +536,42 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
         __syncthreads();
         if (active) (void)bookkeeping(0, false);
         load_row_lane<NV>(row, c.q, p.n);
+        if constexpr (SLIM) {
+            pred_cell = c.q + ((int64_t)p.s * (4 * NV) + p.a);
+            pred_pend = *pred_cell;
+        }
+        if constexpr (SLIM) if (active) lds.acct[0][i] = make_uint2(__float_as_uint(p.r), p.term ? 1u : 0u);
     }
     __syncthreads();
     DeltaEntry* dl = c.dlog ? c.dlog + c.dlog_base + ii : nullptr;  // this agent's record of step 0
     const long long dl_steps = c.dlog ? (c.dlog_cap - c.dlog_base) / c.N : 0;  // steps whose records all fit
     // schedule values are fetched one step ahead of their use (scalar loads whose latency would otherwise
     // sit in front of the update / the selection of every step)
-    int vzero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
+    // (SLIM builds: none of this -- the helper wavefronts put both values into the ring slot of the step's draws)
+    int vzero = 0;
+    if constexpr (!SLIM) asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
     // Schedule values of the coming step, in flight since the step before (see below): taken over behind the explicit wait of
     // the step that uses them, by moves the compiler cannot see through.  (As plain copies at the END of the step --
     // `lr_t = lr_next` -- they were a use of loaded values there, and the compiler put an `s_waitcnt vmcnt(0)` behind the step
     // barrier of EVERY step: a wait for the row gather and the table store, in front of the work that was meant to run under them.)
-    double lr_pend = ((const double*)(uintptr_t)c.lr)[vzero];
-    unsigned long long thr_pend = ((const unsigned long long*)(uintptr_t)c.thr)[(steps > 1 ? 1 : 0) + vzero];
+    double lr_pend = 0.0;
+    unsigned long long thr_pend = 0;
+    if constexpr (!SLIM) {
+        lr_pend = ((const double*)(uintptr_t)c.lr)[vzero];
+        thr_pend = ((const unsigned long long*)(uintptr_t)c.thr)[(steps > 1 ? 1 : 0) + vzero];
+    }
     for (long long t = 0; t < steps; ++t) {
         const bool last = t + 1 == steps;
         const bool dl_ok = t < dl_steps;
         QL_STAMP(7);
         const bool busy = lds.busy[t & 3] != 0u;
         const U4 x = draws(t + 1);
+        double lr_ring = 0.0;  // SLIM builds: lr[t] and thr[t + 1] from the same ring slot (one address for all lanes: a broadcast)
+        unsigned long long thr_ring = 0;
+        if constexpr (SLIM) { lr_ring = lds.sched[(t + 1) & 1].lr; thr_ring = lds.sched[(t + 1) & 1].thr; }
         if (helper && !last && !QX(5)) produce(t + 2);
+        // SLIM builds: the helpers keep the running returns and the episode log
+        if constexpr (SLIM) if (helper) helper_account(t);
         if (stale && !QX(8)) load_row_lane<NV>(row, c.q, p.n);
         const M valid = valid_mask_lane<Env, NV, MASKED>(ev, ii, p.n);
         QL_STAMP(0);
@@ -528,10 +646,17 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
         // of it that wait would be a wait for their round trip as well (a cache miss every eighth step).
         double lr_t;
         unsigned long long thr_t1;
-        asm volatile("v_mov_b64 %0, %1" : "=v"(lr_t) : "v"(lr_pend));
-        asm volatile("v_mov_b64 %0, %1" : "=v"(thr_t1) : "v"(thr_pend));
-        lr_pend = ((const double*)(uintptr_t)c.lr)[(last ? t : t + 1) + vzero];
-        thr_pend = ((const unsigned long long*)(uintptr_t)c.thr)[(t + 2 < steps ? t + 2 : steps - 1) + vzero];
+        if constexpr (SLIM) {
+            lr_t = lr_ring;
+            thr_t1 = thr_ring;
+        } else {
+            asm volatile("v_mov_b64 %0, %1" : "=v"(lr_t) : "v"(lr_pend));
+            asm volatile("v_mov_b64 %0, %1" : "=v"(thr_t1) : "v"(thr_pend));
+            lr_pend = ((const double*)(uintptr_t)c.lr)[(last ? t : t + 1) + vzero];
+            thr_pend = ((const unsigned long long*)(uintptr_t)c.thr)[(t + 2 < steps ? t + 2 : steps - 1) + vzero];
+        }
+        // SLIM builds: Q[p.s, p.a], in flight since the gather of the step before (same take-over as above)
+        if constexpr (SLIM) p.pred = opaque_copy(pred_pend);
         const float r_t = p.r;
         const bool term_t = p.term;
         // ---- update of transition t for agents that may go now ----------------------------------
@@ -546,7 +671,8 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
             T u;
             const T q1 = Td<T>::apply(p.pred, p.r, m, p.term, make_hyper(c, lr_t), c.mode, &u);
             if (p.n == p.s) row_nan |= q1 != q1;
-            if (!QX(1)) c.q[cell] = q1;
+            if constexpr (SLIM) *pred_cell = q1;  // (the address the value was read from)
+            else if (!QX(1)) c.q[cell] = q1;
             // delta log of the replica exchange: a running pointer (slot = base + t * N + agent)
             if (dl_ok) *dl = DeltaEntry{(uint32_t)cell, (float)u};
             if (p.n == p.s) {  // own write lands in the row held in registers
@@ -556,11 +682,14 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
         }
         // base_runtime.py:212,218-221 for transition t.  An episode that ends is staged in LDS (flushed in
         // bulk): ONE returning LDS atomic per wavefront reserves the slots of all its lanes, and its result
-        // is only consumed at the end of the step (ep_store below), so no LDS round trip sits here.
+        // is only consumed at the end of the step (ep_store below).  (The compiler rewrites that single-lane atomic
+        // into its wave-aggregated form, which broadcasts the result with a v_readfirstlane right behind it: an LDS
+        // round trip does sit here.  SLIM builds: none of this -- the agent's helper lane does it in helper_account,
+        // from the {reward, terminated} pair handed over behind the row gather.)
         unsigned ep_raw = 0;       // what the reserving lane's atomic returned (consumed at the end of the step)
         unsigned long long enders = 0;
         float ep_value = 0.0f;
-        if (active) {
+        if (!SLIM && active) {
             acc += r_t;
             enders = __ballot(term_t && (flags & FLAG_ACCOUNT));
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(enders >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)enders, 0u));
@@ -727,6 +856,7 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
             }
         }
         // ---- bulk flush of the staged episode log (uniform, data-independent decision) ----------
+        // (SLIM builds: the helpers staged the entries of step t at its top, in front of this barrier like everybody's)
         if (--flush_in == 0 || last) {
             flush_in = flush_every;
             __syncthreads();
@@ -751,10 +881,20 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
         if (tid == 0) lds.busy[(t + 3) & 3] = 0u;  // flag of step t-1: every wave has read it since
         asm volatile("" ::: "memory");  // the gather stays behind every store of this step (vmcnt counts in order)
         if (!helper && !worker && !QX(0)) load_row_lane<NV>(row, c.q, p.n);
+        if constexpr (SLIM) {
+            // the cell just picked, for the update of the next step: one more load in flight across the barrier
+            if (!helper && !worker) {
+                pred_cell = c.q + ((int64_t)p.s * (4 * NV) + p.a);
+                pred_pend = *pred_cell;
+            }
+        }
+        // ... and its reward and end flag go to the agent's helper lane, which accounts them at the top of step t + 1
+        if constexpr (SLIM) if (active) lds.acct[(t + 1) & 1][i] = make_uint2(__float_as_uint(p.r), p.term ? 1u : 0u);
         asm volatile("" ::: "memory");
         if (active && !QX(2)) stale = bookkeeping(t + 1, true);
         QL_STAMP(1);
-        if (!QX(4)) step_barrier<NLOAD>();  // table writes of step t are complete; the sets of steps t+1, t+2 are in
+        // table writes of step t are complete; the sets of steps t+1, t+2 are in
+        if (!QX(4)) step_barrier<NLOAD + (SLIM ? 1 : 0)>();
         if (c.dlog) dl += c.N;
     }
 #ifdef QE_STAMPS
@@ -762,8 +902,16 @@ __global__ __launch_bounds__(HELP ? 4 * CAP : CAP) void k_rollout_lane(InlineSch
 #endif
     const Ctx<T>& cc = *reinterpret_cast<const Ctx<T>*>(lds.cold);
     if (active) {
-        cc.n[i] = p.n; cc.aux[i] = p.aux; cc.acc[i] = acc;
-        if (cc.hb) { cc.hb_obs[i] = p.n; cc.hb_aux[i] = p.aux; cc.hb_acc[i] = acc; }
+        cc.n[i] = p.n; cc.aux[i] = p.aux;
+        if constexpr (!SLIM) cc.acc[i] = acc;
+        if (cc.hb) {
+            cc.hb_obs[i] = p.n; cc.hb_aux[i] = p.aux;
+            if constexpr (!SLIM) cc.hb_acc[i] = acc;
+        }
+    }
+    if constexpr (SLIM) if (helper) {  // the running returns live on the helper lanes
+        cc.acc[ii] = acc;
+        if (cc.hb) cc.hb_acc[ii] = acc;
     }
     if (tid == 0) {
         cc.ctrl->involved_total = deferred_total;
