@@ -42,6 +42,9 @@ struct Transition {
 template <class WordFn>
 __device__ __forceinline__ uint32_t valid4_from_words(WordFn word, int sub, int A) {
     const int c = 4 * sub;
+    // a lane group is wider than the row once ld > 64 (L = 32 / 64 lanes for ld 68..256): the lanes past the last
+    // column must not ask for a word, the source holds exactly ceil(A / 32) of them per row
+    if (c >= A) return 0u;
     uint32_t bits = (word(c >> 5) >> (c & 31)) & 0xFu;
     return bits & in_range4(sub, A);
 }

@@ -1240,8 +1240,11 @@ __global__ __launch_bounds__(FAST_BLOCK) void k_select(Ctx<T> c, EnvCtx ev, cons
     T picked;
     int act = select_action(row, valid, sub, c.L, explore, x.y, x.z, &picked, (deterministic & 4) != 0);
     // NumPy variants of the reference, agent without a valid action: where(mask, Q, -inf) is all -inf, so
-    // every action ties at the maximum and the greedy pick is uniform over ALL actions (:497-503, :618-628)
-    if (act == -1 && (deterministic & 2) && ev.masked && !explore) act = (int)mulhi32(x.z, (uint32_t)c.A);
+    // every action ties at the maximum and the greedy pick is uniform over ALL actions (:497-503, :618-628).  The
+    // same holds when valid actions exist but every one of them holds -inf: the masked-out columns tie with them
+    // (`picked` is the maximum of a greedy pick).
+    if ((act == -1 || (act >= 0 && picked == neg_inf<T>())) && (deterministic & 2) && ev.masked && !explore)
+        act = (int)mulhi32(x.z, (uint32_t)c.A);
     if (sub == 0) out[i] = act;
 }
 
@@ -1285,7 +1288,9 @@ __global__ __launch_bounds__(FAST_BLOCK) void k_select_large(Ctx<T> c, EnvCtx ev
             k -= cnt;
         }
     }
-    if (act < 0 && (deterministic & 2) && mw != nullptr && !explore && m == m) act = (int)mulhi32(x.z, (uint32_t)c.A);  // see k_select
+    // see k_select: no valid action, or a valid maximum of -inf (m is -inf in both cases)
+    if ((act < 0 || m == neg_inf<T>()) && (deterministic & 2) && mw != nullptr && !explore && m == m)
+        act = (int)mulhi32(x.z, (uint32_t)c.A);
     if (lane == 0) out[i] = act;
 }
 

@@ -176,7 +176,8 @@ int qe_set_agent_offset(qe_engine* e, uint32_t offset); /* draw-protocol id of l
  * `deterministic`: bit 0 = greedy selection (exploration rate ignored); bit 1 (QE_SELECT_NUMPY_EMPTY_MASK)
  * = the NumPy variants' treatment of an agent whose mask has no valid action: its greedy pick is
  * uniform over ALL actions (where(mask, Q, -inf) ties everywhere, :497-503, :618-628), only its
- * exploratory pick is impossible (-1; the reference raises IndexError, :470); bit 2 (QE_SELECT_NUMPY_MAX) = the row
+ * exploratory pick is impossible (-1; the reference raises IndexError, :470); the greedy pick is uniform over ALL
+ * actions too when valid actions exist but every one of them holds -inf (the same tie); bit 2 (QE_SELECT_NUMPY_MAX) = the row
  * maximum is np.max (the NumPy variants, :428, :466, :548, :616): NaN as soon as a valid column holds one, so no
  * action ties with it (-1; the reference raises IndexError) -- without it the list variants' scan, which steps
  * over NaN columns (:290-296, :337-344).  Consumes one step index. */

@@ -52,7 +52,7 @@ class OracleQLearning:
                 best, ties = v, [j]
             elif v == best:
                 ties.append(j)
-        return self._rng.choice(ties) if ties else -1
+        return self._rng.choice(ties) if ties else self._no_candidate()
 
     def choose_masked_action(self, state, action_mask, exploration_rate, *, deterministic=False):
         # :304-348 -- same, restricted to mask-valid actions; the exploratory pick is uniform over

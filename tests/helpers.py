@@ -61,9 +61,11 @@ def schedule_params(kind):
     return ("constant", 1.0, None, None), ("linear", 0.05, None, 0.001)
 
 
-def run_oracle_trace(spec, steps, dt, sched, learn_mode, gamma=0.99, seed=0):
+def run_oracle_trace(spec, steps, dt, sched, learn_mode, gamma=0.99, seed=0, q0=None):
     env = make_oracle_env(spec)
     algo = OracleQLearning(env.state_size, env.action_size, gamma, seed=seed, dtype=np.dtype(dt))
+    if q0 is not None:
+        algo.q_table = np.array(q0, dtype=np.dtype(dt))
     lr_p, eps_p = schedule_params(sched)
     rt = OracleRuntime(algo, OracleSchedule(*lr_p), OracleSchedule(*eps_p), learn_mode=learn_mode)
     rt.trace = []
@@ -91,12 +93,12 @@ def dense_from_sparse(idx, val, shape, dtype):
     return q
 
 
-def run_oracle_chunks(spec, chunks, dt, sched, learn_mode, gamma=0.99, seed=0, q0=None):
+def run_oracle_chunks(spec, chunks, dt, sched, learn_mode, gamma=0.99, seed=0, q0=None, env=None):
     """The closed loop in `chunks` consecutive run_steps-sized pieces.  Returns one dict per chunk with the state at
     its end (q, history so far, obs, acc); a chunk in which the reference's selection raises IndexError (a NaN row
     maximum under a NumPy variant: random.choice([]), q_learning_optimal.py:470, :563) ends the list with
-    {"raised": True}."""
-    env = make_oracle_env(spec)
+    {"raised": True}.  `env`: an oracle-side environment to drive instead of the one `spec` names."""
+    env = make_oracle_env(spec) if env is None else env
     algo = OracleQLearning(env.state_size, env.action_size, gamma, seed=seed, dtype=np.dtype(dt))
     if q0 is not None:
         algo.q_table = np.array(q0, dtype=np.dtype(dt))

@@ -233,10 +233,12 @@ def test_learn_vec_many_collisions_stay_exact():
 PATHS = ["stepwise", "persistent", "wide", "wide_listed", "turnstile", "turnstile_reread"]
 
 
-def _run_product_trace(spec, steps, dt, sched, mode, gamma=0.99, seed=0, path="auto"):
+def _run_product_trace(spec, steps, dt, sched, mode, gamma=0.99, seed=0, path="auto", q0=None, env=None):
     Algo, Runtime, _, _ = _product()
-    env = make_device_env(spec)
+    env = make_device_env(spec) if env is None else env
     algo = Algo(env.state_size, env.action_size, gamma, seed=seed, dtype=np.dtype(dt))
+    if q0 is not None:
+        algo.q_table = np.array(q0, dtype=np.dtype(dt))
     if path == "persistent" and (env.action_size > 64 or env.num_agents > 512):
         pytest.skip("more than 512 agents / 64 actions: the persistent kernel does not apply")
     if path == "turnstile_reread":  # the turnstile path without value forwarding in the progress words
