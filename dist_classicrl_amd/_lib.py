@@ -35,6 +35,7 @@ PATH_AUTO, PATH_STEPWISE, PATH_PERSISTENT, PATH_WIDE, PATH_TURNSTILE = 0, 1, 2, 
 
 RULE_Q_LEARNING, RULE_SARSA, RULE_EXPECTED_SARSA = 0, 1, 2  # qe_update_rule
 N_STEP_MAX = 16  # qe_population_set_n_step
+TREE_BACKUP_MAX = 16  # qe_population_set_tree_backup
 TRACE_MAX = 32  # qe_population_set_traces
 PLANNING_MAX = 64  # qe_population_set_planning
 # qe_population_set_visits: the (table dtype, 16-byte loads per fp32 row) builds of k_visit_rollout that are NOT compiled
@@ -59,7 +60,10 @@ def decode_variant(v: int) -> dict:
     path).  Path 13 (``population_dyna``, kernel ``k_dyna_rollout``) is the Q-learning population with Dyna-Q: NV and
     masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has.  Path 14
     (``population_visit``, kernel ``k_visit_rollout``) is the Q-learning population with visit counts: NV and masked as path
-    6, ``visit_lr`` in bit 4 and ``bonus`` (some run's beta is above 0) in bit 5, two keys that only this path's dict has."""
+    6, ``visit_lr`` in bit 4 and ``bonus`` (some run's beta is above 0) in bit 5, two keys that only this path's dict has.
+    Path 15 (``population_tree``, kernel ``k_tree_rollout``) is the Q-learning population with n-step Tree Backup: NV and
+    masked as path 6 and ``tree_backup``, the horizon, in bits 24-28, a key that only this path's dict has (``n_step`` reads
+    1 there)."""
     v = int(v)
     nstep = (v & 15) == 11
     trace = (v & 15) == 12
@@ -67,7 +71,8 @@ def decode_variant(v: int) -> dict:
     out = {
         "path": {1: "stepwise", 2: "persistent", 3: "wide", 4: "turnstile", 5: "eval", 6: "population",
                  7: "population_eval", 8: "population_td", 9: "population_double", 10: "population_double_eval",
-                 11: "population_nstep", 12: "population_trace", 13: "population_dyna", 14: "population_visit"}.get(v & 15, "none"),
+                 11: "population_nstep", 12: "population_trace", 13: "population_dyna", 14: "population_visit",
+                 15: "population_tree"}.get(v & 15, "none"),
         "rule": ({1: "sarsa", 2: "expected_sarsa"}.get((v >> 4) & 3, "none") if td
                  else {0: "q_learning", 1: "sarsa"}.get((v >> 4) & 3, "none") if trace else "q_learning"),
         "lean": (v >> 4) & 3, "help": bool((v >> 6) & 1), "full": bool((v >> 7) & 1), "light": bool((v >> 8) & 1),
@@ -81,6 +86,8 @@ def decode_variant(v: int) -> dict:
     if (v & 15) == 14:
         out["visit_lr"] = bool((v >> 4) & 1)
         out["bonus"] = bool((v >> 5) & 1)
+    if (v & 15) == 15:
+        out["tree_backup"] = (v >> 24) & 31
     return out
 
 
@@ -244,6 +251,10 @@ PROTOTYPES = {
     "qe_population_n_step": (C.c_int, [_P]),
     "qe_population_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P]),
     "qe_population_set_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P]),
+    "qe_population_set_tree_backup": (C.c_int, [_P, C.c_int32]),
+    "qe_population_tree_backup": (C.c_int, [_P]),
+    "qe_population_tree_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P, _U8P]),
+    "qe_population_set_tree_window": (C.c_int, [_P, _I32P, _I32P, _I32P, _F32P, _U8P]),
     "qe_population_set_traces": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P]),
     "qe_population_trace_config": (C.c_int, [_P, _I32P, _I32P, _F64P]),
     "qe_population_traces": (C.c_int, [_P, _I32P, _I32P, _F64P]),

@@ -35,8 +35,18 @@ besides B.  DESIGN section 4.3c defines the step; ``tests/double_q_model.py`` re
 (Sutton & Barto ch. 7): n-step SARSA and n-step Expected SARSA, the lever between TD(0) and Monte Carlo when reward
 arrives only at the end of an episode.  A run keeps a window of its last transitions; ``state_dict["n_step_window"]``
 carries it from call to call as ``pending_actions`` carries SARSA's action.  An uncorrected n-step Q-learning is not an
-off-policy method, so ``update_rule="q_learning"`` and ``double_q=True`` are refused with ``n_step > 1``.  DESIGN section
-4.3c defines the step; ``tests/n_step_model.py`` restates it on the oracle.
+off-policy method, so ``update_rule="q_learning"`` and ``double_q=True`` are refused with ``n_step > 1``: Q-learning's
+horizon is ``tree_backup``.  DESIGN section 4.3c defines the step; ``tests/n_step_model.py`` restates it on the oracle.
+
+``tree_backup=n`` (2 .. 16, Q-learning only; kernel ``k_tree_rollout``) is that horizon: n-step Tree Backup under a greedy
+target policy (Sutton & Barto 7.5), the off-policy n-step method that needs no importance ratios.  A run keeps a window
+of entries ``(s, a, r, greedy)``; an entry's n-step return passes through the later entries while their actions were
+greedy (``Q[s, a] == max Q[s, valid]`` when they were taken) and stops at the first that was not, where the row maximum
+of that state, read from the table at the update, stands in for the rest.  With epsilon 0 it is n-step Expected SARSA at
+epsilon 0; with ``tree_backup=1`` (the default) it is the one-step Q-learning above, same kernel, nothing allocated.
+``state_dict["tree_backup_window"]`` carries the window from call to call.  Every other rule, ``double_q=True``,
+``n_step > 1``, ``trace_decay``, ``planning_steps > 0``, ``exploration_bonus`` and ``visit_lr`` are refused with it.  DESIGN
+section 4.3c defines the step; ``tests/tree_backup_model.py`` restates it on the oracle.
 
 ``trace_decay=lam`` (one lambda in [0, 1] or one per run; kernel ``k_trace_rollout``) turns on eligibility traces
 (Sutton & Barto ch. 12): SARSA(lambda) under ``update_rule="sarsa"``, Watkins's Q(lambda) under ``"q_learning"`` -- the
@@ -199,6 +209,11 @@ def _window_specs(runs, n_step):
             ("rewards", slots, "fiu", np.float32))
 
 
+def _tree_specs(runs, tree_backup):
+    slots = (runs, tree_backup - 1)
+    return (*_window_specs(runs, tree_backup), ("greedy", slots, "biu", np.uint8))
+
+
 def _trace_specs(runs, trace_length):
     slots = (runs, trace_length)
     return ("states", slots, "iu", np.int32), ("actions", slots, "iu", np.int32), ("values", slots, "fiu", np.float64)
@@ -243,6 +258,20 @@ def window_arrays(window, runs, n_step) -> tuple | None:
     return _spec_arrays("n_step_window", window, _window_specs(runs, n_step))
 
 
+def tree_window_arrays(window, runs, tree_backup) -> tuple | None:
+    """``tree_backup_window`` of a state dict as the ``(length, states, actions, rewards, greedy)`` arrays the library takes
+    (None: every window empty): those of :func:`window_arrays` for ``tree_backup - 1`` slots and uint8 ``[runs,
+    tree_backup - 1]`` (bools or integers; the library refuses a flag other than 0 or 1); ``ValueError`` on anything
+    else."""
+    arrays = _spec_arrays("tree_backup_window", window, _tree_specs(runs, tree_backup))
+    if arrays is not None:
+        flags = np.asarray(window["greedy"])
+        if flags.dtype.kind != "b" and flags.size and (flags.min() < 0 or flags.max() > 1):
+            msg = f"tree_backup_window['greedy']: expected flags 0 or 1, got values in [{flags.min()}, {flags.max()}]"
+            raise ValueError(msg)
+    return arrays
+
+
 def trace_arrays(traces, runs, trace_length) -> tuple | None:
     """``eligibility_traces`` of a state dict as the ``(states, actions, values)`` arrays the library takes (None: every
     slot free): int32 ``[runs, trace_length]`` twice and float64 ``[runs, trace_length]``; ``ValueError`` on anything
@@ -276,7 +305,8 @@ def visit_count_array(counts, runs, state_size, action_size) -> np.ndarray | Non
 # The per-run state a training call hands to the next one through the state dict: the dict's key, which is also the
 # population's property, and whether a population carries it.  (The planning model is knowledge, not such state.)
 _CARRIED = {"pending_actions": lambda pop: pop.update_rule == "sarsa", "n_step_window": lambda pop: pop.n_step > 1,
-            "eligibility_traces": lambda pop: pop.trace_decay is not None}
+            "eligibility_traces": lambda pop: pop.trace_decay is not None,
+            "tree_backup_window": lambda pop: pop.tree_backup > 1}
 
 
 def _check_int(name, value, lo, hi) -> None:
@@ -299,7 +329,8 @@ class QLearningPopulation:
 
     ``discount_factor``, ``lr_schedule`` and ``exploration_rate_schedule`` take one value / schedule for every run or a
     sequence of ``runs``; ``update_rule`` ("q_learning", "sarsa" or "expected_sarsa"), ``double_q`` (two tables per
-    run, Q-learning only) and ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) hold for all of them.
+    run, Q-learning only), ``n_step`` (1 .. 16, above 1 for the two on-policy rules only) and ``tree_backup`` (1 .. 16,
+    above 1 for "q_learning" alone, without any switch below: n-step Tree Backup) hold for all of them.
     ``trace_decay`` (None: no traces; else one lambda in [0, 1] or a sequence of ``runs``) turns on eligibility traces for
     "sarsa" and "q_learning", with ``trace_length`` slots per run (1 .. 32) of ``trace_kind`` "replacing" or
     "accumulating".  ``planning_steps`` (0: none; 1 .. 64) turns on Dyna-Q for "q_learning": that many planning updates
@@ -312,7 +343,7 @@ class QLearningPopulation:
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
                  update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
-                 trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False):
+                 trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False, tree_backup=1):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -338,8 +369,30 @@ class QLearningPopulation:
             raise ValueError(msg)
         if n_step > 1 and update_rule == "q_learning":
             msg = (f"n_step={n_step} needs update_rule='sarsa' or 'expected_sarsa': an uncorrected n-step Q-learning is not an "
-                   "off-policy method (importance sampling and tree backup are not built)")
+                   "off-policy method (Q-learning's n-step form is tree_backup=n)")
             raise ValueError(msg)
+        _check_int("tree_backup", tree_backup, 1, _lib.TREE_BACKUP_MAX)
+        if tree_backup > 1:
+            what = f"tree_backup={tree_backup}"
+            if update_rule != "q_learning":
+                msg = (f"{what} needs update_rule='q_learning', got {update_rule!r}: Tree Backup under a greedy target policy "
+                       "is Q-learning's n-step form; the on-policy rules have n_step")
+                raise ValueError(msg)
+            if double_q:
+                msg = f"{what} with double_q=True: the double estimator is a one-step method"
+                raise ValueError(msg)
+            if n_step > 1:
+                msg = f"{what} with n_step={n_step}: one multi-step method at a time"
+                raise ValueError(msg)
+            if trace_decay is not None:
+                msg = f"{what} with trace_decay: one multi-step method at a time"
+                raise ValueError(msg)
+            if isinstance(planning_steps, (int, np.integer)) and not isinstance(planning_steps, (bool, np.bool_)) and planning_steps > 0:
+                msg = f"{what} with planning_steps={planning_steps}: Dyna-Q is a one-step method"
+                raise ValueError(msg)
+            if exploration_bonus is not None or (isinstance(visit_lr, (bool, np.bool_)) and visit_lr):
+                msg = f"{what} with exploration_bonus or visit_lr: visit counts are built for the one-step rule"
+                raise ValueError(msg)
         _check_int("planning_steps", planning_steps, 0, _lib.PLANNING_MAX)
         if planning_steps > 0:
             if update_rule != "q_learning":
@@ -399,6 +452,7 @@ class QLearningPopulation:
         self.update_rule = update_rule
         self.double_q = bool(double_q)
         self.n_step = int(n_step)
+        self.tree_backup = int(tree_backup)
         self.learn_mode = learn_mode
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.discount_factor = np.ascontiguousarray(_per_run(discount_factor, self.runs, "discount_factor"), dtype=np.float64)
@@ -459,6 +513,8 @@ class QLearningPopulation:
             _lib.check(self._lib.qe_population_set_double(self._h, 1))
         if self.n_step > 1:
             _lib.check(self._lib.qe_population_set_n_step(self._h, self.n_step))
+        if self.tree_backup > 1:
+            _lib.check(self._lib.qe_population_set_tree_backup(self._h, self.tree_backup))
         if self.trace_decay is not None:
             _lib.check(self._lib.qe_population_set_traces(self._h, self.trace_length, _lib.TRACE_KINDS[self.trace_kind],
                                                           _lib.ptr(self.trace_decay, C.c_double)))
@@ -551,6 +607,25 @@ class QLearningPopulation:
                 raise ValueError(msg)
             return
         self._set_state(self._lib.qe_population_set_window, window_arrays(window, self.runs, self.n_step), 4)
+
+    @property
+    def tree_backup_window(self) -> dict | None:
+        """``tree_backup > 1``: every run's window of entries not yet updated, a dict of ``length`` (int32 ``[runs]``),
+        ``states``, ``actions`` (int32 ``[runs, tree_backup - 1]``), ``rewards`` (float32) and ``greedy`` (uint8: 1 where
+        the action was a greedy one when it was taken); rows are oldest first and unused slots hold 0.
+        ``tree_backup == 1``: None.  Setting None empties every window."""
+        if self.tree_backup == 1:
+            return None
+        return self._state_dict_of(self._lib.qe_population_tree_window, _tree_specs(self.runs, self.tree_backup))
+
+    @tree_backup_window.setter
+    def tree_backup_window(self, window) -> None:
+        if self.tree_backup == 1:
+            if window is not None:
+                msg = "a population with tree_backup=1 has no window"
+                raise ValueError(msg)
+            return
+        self._set_state(self._lib.qe_population_set_tree_window, tree_window_arrays(window, self.runs, self.tree_backup), 5)
 
     @property
     def eligibility_traces(self) -> dict | None:
@@ -791,8 +866,8 @@ class QLearningPopulation:
         """``steps`` steps of every run on ``env`` (a device environment of ``num_agents == runs``).  ``curr_state_dict``
         None resets the environment, as the reference's ``run_steps``; the dict of the previous call continues it
         (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step;
-        ``n_step > 1``: with its ``n_step_window``; after a reset, or without that key, every window starts empty and
-        the entries dropped are never updated; ``trace_decay``: with its ``eligibility_traces``; after a reset, or
+        ``n_step > 1`` / ``tree_backup > 1``: with its ``n_step_window`` / ``tree_backup_window``; after a reset, or without
+        that key, every window starts empty and the entries dropped are never updated; ``trace_decay``: with its ``eligibility_traces``; after a reset, or
         without that key, every slot starts free).
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
@@ -839,7 +914,7 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``) window and (``trace_decay``) trace slots.  Tables: :meth:`load`; environments: pass
+        counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``, ``tree_backup > 1``) window and (``trace_decay``) trace slots.  Tables: :meth:`load`; environments: pass
         the dict to ``run_steps``."""
         for key, has in _CARRIED.items():
             if has(self):
@@ -983,4 +1058,5 @@ class QLearningPopulation:
 
 
 __all__ = ["PolicyValues", "PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "visit_count_array", "window_arrays"]
+           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "tree_window_arrays", "visit_count_array",
+           "window_arrays"]

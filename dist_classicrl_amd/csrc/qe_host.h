@@ -27,6 +27,7 @@ using namespace qe;
 
 namespace qe {
 struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
+struct TreeWin;   // the windows of n-step Tree Backup (qe_rollout_tree.h)
 template <typename T>
 struct TraceSlots;  // the slots of the eligibility traces (qe_rollout_trace.h)
 struct DynaModel;   // the learned model and visited list of Dyna-Q (qe_rollout_dyna.h)
@@ -209,6 +210,18 @@ struct PopState {
             n = 1;
         }
     } win;
+    // n-step Tree Backup (qe_population_set_tree_backup): the horizon, 1 = the one-step kernel above.  n > 1: every run's
+    // window of at most n - 1 entries between launches, [slot][runs], oldest first; an action word carries the entry's
+    // greedy flag in its top bit (k_tree_rollout, qe_rollout_tree.h); allocated when the horizon is set.
+    struct TreeWindow {
+        int n = 1;
+        DevBuf<int32_t> len, s, a;
+        DevBuf<float> r;
+        void release() {
+            len.release(); s.release(); a.release(); r.release();
+            n = 1;
+        }
+    } tree;
     // Eligibility traces (qe_population_set_traces): k slots per run, 0 = off (the kernels above).  On: every run's
     // slots between launches, [slot][runs] (e holds k * runs values of the table dtype; a slot whose value is 0 is
     // free), and every run's lambda (k_trace_rollout, qe_rollout_trace.h); allocated when traces are set.
@@ -256,7 +269,7 @@ struct PopState {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void release() {
         eps.release(); lr.release(); gamma.release(); status.release(); ep_count.release(); ep_sum.release();
-        log.release(); epi.release(); win.release(); trace.release(); dyna.release(); visit.release();
+        log.release(); epi.release(); win.release(); tree.release(); trace.release(); dyna.release(); visit.release();
         step_off.release(); pending.release();
         if (table_b) (void)hipFree(table_b);
         table_b = nullptr;
@@ -487,7 +500,8 @@ constexpr int GRAPH_STEPS = 50;  // vector steps per captured graph (step-wise /
 //   rule in bits 4-5 (0 = Watkins's Q(lambda), 1 = SARSA(lambda)), NV and masked as path 6, K in bits 24-29 and the trace
 //   kind in bit 30, which no other field of that path uses; path 13 = population with Dyna-Q (k_dyna_rollout): NV and
 //   masked as path 6, and the planning updates per step in bits 24-30; path 14 = population with visit counts
-//   (k_visit_rollout): NV and masked as path 6, visit_lr in bit 4 and "some beta > 0" in bit 5
+//   (k_visit_rollout): NV and masked as path 6, visit_lr in bit 4 and "some beta > 0" in bit 5; path 15 = population with
+//   n-step Tree Backup (k_tree_rollout): NV and masked as path 6, and n in bits 24-28
 constexpr int64_t QE_VARIANT_DATAFLOW = 1 << 10;  // persistent path: k_rollout_df (qe_rollout_df.h)
 constexpr int64_t QE_VARIANT_STEPWISE = (int64_t)RolloutPath::Stepwise, QE_VARIANT_PERSISTENT = (int64_t)RolloutPath::Persistent,
                   QE_VARIANT_WIDE = (int64_t)RolloutPath::Wide, QE_VARIANT_TURNSTILE = (int64_t)RolloutPath::Turnstile,
@@ -501,6 +515,7 @@ constexpr int64_t QE_VARIANT_RUNS_NSTEP = 11;  // population, n-step SARSA / Exp
 constexpr int64_t QE_VARIANT_RUNS_DYNA = 13;   // population, Dyna-Q (k_dyna_rollout): NV and masked bits, + planning updates in bits 24-30
 constexpr int64_t QE_VARIANT_RUNS_TRACE = 12;  // population, SARSA(lambda) / Watkins's Q(lambda) (k_trace_rollout): + K in bits 24-29, kind in bit 30
 constexpr int64_t QE_VARIANT_RUNS_VISIT = 14;  // population, visit counts (k_visit_rollout): NV and masked bits, + visit_lr in bit 4, bonus in bit 5
+constexpr int64_t QE_VARIANT_RUNS_TREE = 15;   // population, n-step Tree Backup (k_tree_rollout): NV and masked bits, + n in bits 24-28
 // build: 1 dataflow, 2 full, 3 sparse (lane_build in qe_engine.hip; the generic builds take what these do not)
 template <typename T, class Env>
 int launch_persistent(qe_engine* e, qe_env* env, RolloutSlot& sl, const Ctx<T>& c, const EnvCtx& ev, int64_t steps, int mode,
@@ -562,6 +577,9 @@ int64_t launch_runs_td(const RunsLaunch<T>& l, int rule, int32_t* pending);
 // ... with the n-step form of that rule and the runs' windows `w` (qe_inst_runs_nstep.hip)
 template <typename T, class Env>
 int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const NStepWin& w);
+// ... with n-step Tree Backup, Q-learning's n-step form, and the runs' windows `w` (qe_inst_runs_tree.hip)
+template <typename T, class Env>
+int64_t launch_tree_runs(const RunsLaunch<T>& l, const TreeWin& w);
 // ... with eligibility traces: `rule` is QE_RULE_Q_LEARNING or QE_RULE_SARSA, `w` the runs' slots (qe_inst_runs_trace.hip)
 template <typename T, class Env>
 int64_t launch_trace_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const TraceSlots<T>& w);

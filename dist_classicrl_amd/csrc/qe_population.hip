@@ -6,6 +6,7 @@
 #include "qe_rollout_dyna.h"
 #include "qe_rollout_nstep.h"
 #include "qe_rollout_trace.h"
+#include "qe_rollout_tree.h"
 #include "qe_rollout_visit.h"
 
 namespace {
@@ -203,6 +204,22 @@ int window_reserve(qe_engine* e, int n) {
     return QE_OK;
 }
 
+// Tree Backup's windows, [slot][runs] with n - 1 slots: allocated for the horizon `n`, every window empty.
+int tree_reserve(qe_engine* e, int n) {
+    PopState::TreeWindow& W = e->pop.tree;
+    const size_t m = (size_t)e->pop.runs, cells = m * (size_t)(n - 1);
+    HIP_TRY(W.len.ensure(m)); HIP_TRY(W.s.ensure(cells)); HIP_TRY(W.a.ensure(cells)); HIP_TRY(W.r.ensure(cells));
+    HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
+// What every other mode setter answers while Tree Backup is on.
+int tree_refuse(const qe_engine* e, const char* what) {
+    return qe_fail(QE_ERR_UNSUPPORTED, "%s: tree_backup = %d is on, and Tree Backup is built for the plain Q-learning run (qe_population_set_tree_backup)",
+                   what, e->pop.tree.n);
+}
+
 // T(gamma * lambda), the decay factor of a run's traces, as a double; `f32`: T is float.
 double trace_decay_of(double gamma, double lambda, bool f32) {
     const double d = gamma * lambda;
@@ -300,6 +317,7 @@ int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
     if (P.trace.k)
         return launch_trace_runs<T, Env>(l, P.rule, P.pending.p,
                                          TraceSlots<T>{P.trace.k, P.trace.kind, P.trace.s.p, P.trace.a.p, (T*)P.trace.e.p, P.trace.lambda.p});
+    if (P.tree.n > 1) return launch_tree_runs<T, Env>(l, TreeWin{P.tree.n, P.tree.len.p, P.tree.s.p, P.tree.a.p, P.tree.r.p});
     if (P.win.n > 1) return launch_nstep_runs<T, Env>(l, P.rule, P.pending.p, NStepWin{P.win.n, P.win.len.p, P.win.s.p, P.win.a.p, P.win.r.p});
     if (P.rule != QE_RULE_Q_LEARNING) return launch_runs_td<T, Env>(l, P.rule, P.pending.p);
     return launch_runs<T, Env>(l);
@@ -606,12 +624,13 @@ int qe_population_set_update_rule(qe_engine* e, int32_t rule) {
     if (rule != QE_RULE_Q_LEARNING && rule != QE_RULE_SARSA && rule != QE_RULE_EXPECTED_SARSA)
         return qe_fail(QE_ERR_INVALID, "unknown update rule %d (qe_update_rule)", (int)rule);
     if (e->pop.visit.on && rule != QE_RULE_Q_LEARNING) return visits_refuse("an on-policy update rule");
+    if (e->pop.tree.n > 1 && rule != QE_RULE_Q_LEARNING) return tree_refuse(e, "an on-policy update rule");
     if (e->pop.table_b && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED, "the double estimator is built for Q-learning only (qe_population_set_double)");
     if (e->pop.win.n > 1 && rule == QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
-                       "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (importance sampling and "
-                       "tree backup are not built); the n-step rules are SARSA and Expected SARSA",
+                       "n_step = %d: an uncorrected n-step Q-learning is not an off-policy method (its n-step form is Tree Backup, "
+                       "qe_population_set_tree_backup); the n-step rules are SARSA and Expected SARSA",
                        e->pop.win.n);
     if (e->pop.dyna.planning && rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
@@ -635,6 +654,7 @@ int qe_population_set_double(qe_engine* e, int32_t on) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
     if (on && P.visit.on) return visits_refuse("the double estimator");
+    if (on && P.tree.n > 1) return tree_refuse(e, "the double estimator");
     if (on && P.win.n > 1)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_n_step)", P.win.n);
     if (on && P.trace.k)
@@ -729,10 +749,11 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
     PopState& P = e->pop;
     if (n < 1 || n > NSTEP_MAX) return qe_fail(QE_ERR_INVALID, "n_step must be in 1 .. %d, got %d", NSTEP_MAX, (int)n);
     if (n > 1 && P.visit.on) return visits_refuse("n_step > 1");
+    if (n > 1 && P.tree.n > 1) return tree_refuse(e, "n_step > 1");
     if (n > 1 && P.rule == QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
-                       "n_step = %d with Q-learning: an uncorrected n-step Q-learning is not an off-policy method (importance "
-                       "sampling and tree backup are not built); the n-step rules are SARSA and Expected SARSA",
+                       "n_step = %d with Q-learning: an uncorrected n-step Q-learning is not an off-policy method (its n-step form is "
+                       "Tree Backup, qe_population_set_tree_backup); the n-step rules are SARSA and Expected SARSA",
                        (int)n);
     if (n > 1 && P.table_b)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
@@ -820,6 +841,112 @@ int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* st
     return QE_OK;
 }
 
+int qe_population_set_tree_backup(qe_engine* e, int32_t n) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (n < 1 || n > TREE_MAX) return qe_fail(QE_ERR_INVALID, "tree_backup must be in 1 .. %d, got %d", TREE_MAX, (int)n);
+    if (n > 1 && P.visit.on) return visits_refuse("tree_backup > 1");
+    if (n > 1 && P.rule != QE_RULE_Q_LEARNING)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "tree_backup = %d with update rule %d: Tree Backup under a greedy target policy is Q-learning's n-step form; "
+                       "the on-policy rules have n_step (qe_population_set_n_step)",
+                       (int)n, P.rule);
+    if (n > 1 && P.table_b)
+        return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d: the double estimator is a one-step method (qe_population_set_double)", (int)n);
+    if (n > 1 && P.win.n > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d with n_step = %d: one multi-step method at a time (qe_population_set_n_step)", (int)n, P.win.n);
+    if (n > 1 && P.trace.k)
+        return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
+    if (n > 1 && P.dyna.planning)
+        return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)", (int)n);
+    if (n == P.tree.n) return QE_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (n > 1) {
+        if (int rc = tree_reserve(e, n)) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        P.tree.release();
+    }
+    P.tree.n = n;
+    return QE_OK;
+}
+
+int qe_population_tree_backup(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    return e->pop.tree.n;
+}
+
+int qe_population_tree_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards, uint8_t* greedy) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs, w = (size_t)(P.tree.n - 1);
+    if (!w) return QE_OK;  // the one-step rule has no window: nothing to write
+    if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hs(m * w), ha(m * w), hf(m * w);
+    std::vector<float> hr(m * w);
+    HIP_TRY(hipMemcpyAsync(len, P.tree.len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), P.tree.s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), P.tree.a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), P.tree.r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < m * w; ++k) {  // the action word: the action, and the flag in its top bit
+        hf[k] = ha[k] < 0 ? 1 : 0;
+        ha[k] &= ~TREE_GREEDY;
+    }
+    auto used = [&](size_t r, size_t i) { return (int32_t)i < len[r]; };  // slots past the length hold 0
+    slots_to_abi(hs.data(), states, m, w, used);
+    slots_to_abi(ha.data(), actions, m, w, used);
+    slots_to_abi(hr.data(), rewards, m, w, used);
+    slots_to_abi(hf.data(), greedy, m, w, used);
+    return QE_OK;
+}
+
+int qe_population_set_tree_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
+                                  const float* rewards, const uint8_t* greedy) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    const size_t m = (size_t)P.runs, w = (size_t)(P.tree.n - 1);
+    if (!w) {
+        for (size_t r = 0; len && r < m; ++r)
+            if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with tree_backup = 1", (long long)r, (int)len[r]);
+        return QE_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!len) {  // every window empty
+        HIP_TRY(hipMemsetAsync(P.tree.len.p, 0, m * sizeof(int32_t), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return QE_OK;
+    }
+    if (!states || !actions || !rewards || !greedy) return qe_fail(QE_ERR_INVALID, "states, actions, rewards or greedy is NULL");
+    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
+        if (len[r] < 0 || len[r] > (int32_t)w)
+            return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
+        for (size_t i = 0; i < (size_t)len[r]; ++i) {
+            const int32_t s = states[r * w + i], a = actions[r * w + i];
+            if (s < 0 || s >= P.S)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)P.S);
+            if (a < 0 || a >= e->A)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
+            if (greedy[r * w + i] > 1)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: greedy flag %d is neither 0 nor 1", (long long)r, (int)greedy[r * w + i]);
+        }
+    }
+    std::vector<int32_t> hs(m * w), ha(m * w), packed(m * w);
+    std::vector<float> hr(m * w);
+    for (size_t k = 0; k < m * w; ++k) packed[k] = actions[k] | (greedy[k] ? TREE_GREEDY : 0);
+    auto used = [&](size_t r, size_t i) { return i < (size_t)len[r]; };
+    slots_to_device(states, hs.data(), m, w, used);
+    slots_to_device(packed.data(), ha.data(), m, w, used);
+    slots_to_device(rewards, hr.data(), m, w, used);
+    HIP_TRY(hipMemcpyAsync(P.tree.len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.tree.s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.tree.a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.tree.r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double* lambda) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
@@ -835,6 +962,7 @@ int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double
     if (kind != QE_TRACE_REPLACING && kind != QE_TRACE_ACCUMULATING)
         return qe_fail(QE_ERR_INVALID, "unknown trace kind %d (qe_trace_kind)", (int)kind);
     if (P.visit.on) return visits_refuse("eligibility traces");
+    if (P.tree.n > 1) return tree_refuse(e, "eligibility traces");
     for (size_t r = 0; r < m; ++r)
         if (!(lambda[r] >= 0.0 && lambda[r] <= 1.0))
             return qe_fail(QE_ERR_UNSUPPORTED, "trace decay of run %lld: lambda = %g is outside [0, 1]", (long long)r, lambda[r]);
@@ -948,6 +1076,7 @@ int qe_population_set_planning(qe_engine* e, int32_t n) {
         return QE_OK;
     }
     if (P.visit.on) return visits_refuse("planning");
+    if (P.tree.n > 1) return tree_refuse(e, "planning");
     if (P.rule != QE_RULE_Q_LEARNING)
         return qe_fail(QE_ERR_UNSUPPORTED,
                        "planning with update rule %d: Dyna-Q replays remembered transitions through Q-learning's update; planning "
@@ -1096,6 +1225,7 @@ int qe_population_set_visits(qe_engine* e, const double* bonus, int32_t visit_lr
                        "visit counts with update rule %d: the bonus changes the behaviour policy only, and the on-policy rules "
                        "under a bonus policy are not built",
                        P.rule);
+    if (P.tree.n > 1) return tree_refuse(e, "visit counts");
     if (P.table_b) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: the double estimator is on (qe_population_set_double)");
     if (P.win.n > 1) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts with n_step = %d: they are built for the one-step rule (qe_population_set_n_step)", P.win.n);
     if (P.trace.k) return qe_fail(QE_ERR_UNSUPPORTED, "visit counts: eligibility traces are on (qe_population_set_traces)");

@@ -104,7 +104,8 @@ typedef struct qe_rollout_stats {
                                 population with Dyna-Q (qe_population_set_planning): NV and masked as path 6, and the
                                 planning updates per step in bits 24-30; path 14: population with visit counts
                                 (qe_population_set_visits): NV and masked as path 6, visit_lr in bit 4 and "some run's
-                                beta is above 0" in bit 5 */
+                                beta is above 0" in bit 5; path 15: population with n-step Tree Backup
+                                (qe_population_set_tree_backup): NV and masked as path 6, and n in bits 24-28 */
     int64_t complex_steps;   /* persistent path: vector steps that needed the general ordered path (full build); the
                                 dataflow kernel reports its dataflow rounds beyond the first of a step instead */
 } qe_rollout_stats;
@@ -368,7 +369,7 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         later rewards onto the one-step rule's scalar v of this step: g_L = v, g_i = T(r_i + gamma *
  *                         g_{i+1}), with the arithmetic of the learn mode.  Setting n empties every window.  Not a
  *                         population engine or n out of range -> QE_ERR_INVALID.  n > 1 while the rule is Q-learning (an
- *                         uncorrected n-step Q-learning is no off-policy method) or the double switch is on ->
+ *                         uncorrected n-step Q-learning is no off-policy method; qe_population_set_tree_backup is) or the double switch is on ->
  *                         QE_ERR_UNSUPPORTED, and so is switching to either of those while n > 1.  Greedy evaluation
  *                         neither reads nor clears the windows.
  *   qe_population_window / qe_population_set_window  the windows, run state besides the tables and the pending actions:
@@ -377,6 +378,27 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         rollout leaves them behind; set them (len NULL: every window empty, its entries are never
  *                         updated) when the environment state is restored or reset.  A length above n - 1, or a state or
  *                         action outside the table -> QE_ERR_INVALID.  With n = 1 there is nothing to read or set.
+ *   qe_population_set_tree_backup / qe_population_tree_backup  n-step Tree Backup under a greedy target policy (Sutton &
+ *                         Barto 7.5), the n-step form of Q-learning: the horizon n, 1 (the default: the one-step kernel,
+ *                         nothing allocated) .. 16.  An orthogonal switch like the double estimator, not an update rule and
+ *                         not n_step.  A run keeps a window of entries (s, a, r, f), at most n - 1 between steps; f says
+ *                         whether a was greedy: Q[s, a] == np.max(Q[s, valid]) on the row the pick saw (a NaN maximum is
+ *                         never equal).  A step is Q-learning's step up to the bootstrap v = np.max(Q[s', valid]); it
+ *                         appends its entry; a window of n entries updates and drops its oldest one, a terminated step
+ *                         updates all of them, oldest first, and empties the window.  Entry j bootstraps from g_{j+1}:
+ *                         g_L = v; for j < i < L, g_i = T(r_i + gamma * g_{i+1}) with the arithmetic of the learn mode if
+ *                         f_i, else np.max(Q[s_i, valid(s_i)]) as the table stands at that update -- so only the nearest
+ *                         non-greedy entry after j matters, and the flag of entry j itself is not read.  Setting n empties
+ *                         every window.  Not a population engine or n out of range -> QE_ERR_INVALID.  n > 1 while the rule
+ *                         is not Q-learning, the double switch is on, n_step > 1, traces are on, planning is on or visit
+ *                         counts are on -> QE_ERR_UNSUPPORTED, and so is switching to any of those while n > 1.  Greedy
+ *                         evaluation neither reads nor clears the windows.
+ *   qe_population_tree_window / qe_population_set_tree_window  those windows, run state besides the tables: `len` has
+ *                         `runs` entries (0 .. n - 1), `states`, `actions`, `rewards` and `greedy` (0 or 1) runs * (n - 1),
+ *                         run r's entries at [r * (n - 1) + i], oldest first; unused slots read 0 and are ignored when set.
+ *                         Set them (len NULL: every window empty, its entries are never updated) when the environment
+ *                         state is restored or reset.  A length above n - 1, a state or action outside the table, or a flag
+ *                         other than 0 or 1 -> QE_ERR_INVALID.  With n = 1 there is nothing to read or set.
  *   qe_population_set_traces  eligibility traces (Sutton & Barto ch. 12): SARSA(lambda) under QE_RULE_SARSA, Watkins's
  *                         Q(lambda) under QE_RULE_Q_LEARNING.  `lambda` has `runs` entries in [0, 1]; NULL turns traces off
  *                         (the one-step kernels, the default) and frees the slots.  Every run keeps K slots (s_i, a_i, e_i),
@@ -484,6 +506,11 @@ int qe_population_n_step(qe_engine* e);
 int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards);
 int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
                              const float* rewards);
+int qe_population_set_tree_backup(qe_engine* e, int32_t n);
+int qe_population_tree_backup(qe_engine* e);
+int qe_population_tree_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards, uint8_t* greedy);
+int qe_population_set_tree_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
+                                  const float* rewards, const uint8_t* greedy);
 int qe_population_set_traces(qe_engine* e, int32_t trace_length, int32_t trace_kind, const double* lambda);
 int qe_population_trace_config(qe_engine* e, int32_t* trace_length, int32_t* trace_kind, double* lambda);
 int qe_population_traces(qe_engine* e, int32_t* states, int32_t* actions, double* values);

@@ -4,7 +4,7 @@ rollout on the same environment, measured in the same process.
     python tools/population_rate.py --out DIR [--steps 10000] [--dtype float32] [--quick] [--evaluate]
                                     [--rule q_learning|sarsa|expected_sarsa] [--n-step N] [--double] [--actions A]
                                     [--trace-decay LAMBDA [--trace-length K] [--trace-kind replacing|accumulating]]
-                                    [--planning-steps N] [--exploration-bonus B] [--visit-lr]
+                                    [--planning-steps N] [--exploration-bonus B] [--visit-lr] [--tree-backup N]
 
 Workloads: a FrozenLake-8x8-slippery-like TabularMDPEnv (64 states x 4 actions, 3 outcomes per move, built here) at
 M in {64, 1024, 4096, 65536} runs with and without the episode log; TicTacToe at M = 1024; a 1e4 x 8 HashTabularEnv at
@@ -25,6 +25,8 @@ run's learned model after every step; writes DIR/population_rate_dyna<N>.json, w
 --exploration-bonus B (B >= 0) and --visit-lr (with --rule q_learning) train with visit counts (k_visit_rollout): the
 bonus B / sqrt(N(s, a)) on the pick and / or the learning rate divided by N(s, a); writes DIR/population_rate_visit.json,
 with the event time per env-step beside the wall rate.
+--tree-backup N (2 .. 16, with --rule q_learning; 1 is the plain run) trains with n-step Tree Backup (k_tree_rollout) and
+writes DIR/population_rate_tree<N>.json, with the event time per env-step beside the wall rate.
 --double trains (or, with --evaluate, evaluates) a Double Q-learning population (double_q=True: k_double_rollout /
 k_double_evaluate, two tables per run) against the same single-table standalone baseline and writes
 DIR/population_rate_double.json (DIR/population_eval_rate_double.json).
@@ -85,7 +87,7 @@ def schedules():
 
 
 def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", double_q=False, n_step=1, traces=None,
-                    planning=0, bonus=None, visit_lr=False):
+                    planning=0, bonus=None, visit_lr=False, tree_backup=1):
     lr, eps = schedules()
     kw = {} if rule == "q_learning" else {"update_rule": rule}
     if n_step != 1:
@@ -100,6 +102,8 @@ def population_rate(make_env, M, S, A, steps, dtype, log, rule="q_learning", dou
         kw["exploration_bonus"] = bonus
     if visit_lr:
         kw["visit_lr"] = True
+    if tree_backup != 1:
+        kw["tree_backup"] = tree_backup
     pop = QLearningPopulation(M, S, A, 0.99, lr, eps, seed=1, dtype=dtype, **kw)
     env = make_env(M)
     res = pop.run_steps(min(200, steps), env, log=log)  # warm-up: code objects, allocations
@@ -169,6 +173,7 @@ def main() -> None:
     ap.add_argument("--planning-steps", type=int, default=0, help="Dyna-Q planning updates per step (0 .. 64; q_learning only)")
     ap.add_argument("--exploration-bonus", type=float, default=None, help="beta of the count-based bonus beta / sqrt(N(s, a)) (q_learning only)")
     ap.add_argument("--visit-lr", action="store_true", help="learning rate divided by the visit count N(s, a) (q_learning only)")
+    ap.add_argument("--tree-backup", type=int, default=1, help="horizon of n-step Tree Backup (1 .. 16; q_learning only)")
     ap.add_argument("--actions", type=int, default=0, help="also measure a 1e4-state HashTabularEnv with this many actions")
     args = ap.parse_args()
     if args.evaluate and args.rule != "q_learning":
@@ -187,6 +192,10 @@ def main() -> None:
                      or args.evaluate):
         ap.error("--exploration-bonus and --visit-lr go with --rule q_learning (training runs), without --double, --n-step, "
                  "--trace-decay and --planning-steps")
+    if args.tree_backup != 1 and (args.rule != "q_learning" or args.double or args.n_step != 1 or args.trace_decay is not None
+                                  or args.planning_steps or counting or args.evaluate):
+        ap.error("--tree-backup goes with --rule q_learning (training runs), without --double, --n-step, --trace-decay, "
+                 "--planning-steps, --exploration-bonus and --visit-lr")
     traces = None if args.trace_decay is None else (args.trace_decay, args.trace_length, args.trace_kind)
     dtype = np.dtype(args.dtype)
     steps = 1000 if args.quick else args.steps
@@ -216,7 +225,10 @@ def main() -> None:
             pop = population_eval_rate(make_env, M, S, A, k, dtype, log, args.double)
         else:
             pop = population_rate(make_env, M, S, A, k, dtype, log, args.rule, args.double, args.n_step, traces,
-                                  args.planning_steps, args.exploration_bonus, args.visit_lr)
+                                  args.planning_steps, args.exploration_bonus, args.visit_lr, args.tree_backup)
+            if args.tree_backup != 1:
+                pop["tree_backup"] = args.tree_backup
+                pop["event_ns_per_env_step"] = pop["kernel_ms"] * 1e6 / (pop["runs"] * pop["steps"])
             if counting:
                 pop["exploration_bonus"] = args.exploration_bonus
                 pop["visit_lr"] = args.visit_lr
@@ -242,6 +254,8 @@ def main() -> None:
         name = f"population_rate_dyna{args.planning_steps}.json"
     if counting:
         name = "population_rate_visit.json"
+    if args.tree_backup != 1:
+        name = f"population_rate_tree{args.tree_backup}.json"
     if args.double:
         name = name.replace(".json", "_double.json")
     (args.out / name).write_text(json.dumps(lines, indent=1))
