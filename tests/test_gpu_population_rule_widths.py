@@ -1,14 +1,16 @@
 """GPU: the population's later update rules -- SARSA and Expected SARSA (k_rollout_runs_td), n-step (k_nstep_rollout),
-eligibility traces (k_trace_rollout), Dyna-Q (k_dyna_rollout), Double Q (k_double_rollout) and the two greedy-evaluation
-kernels -- at the places the Q-learning kernel was already taken to (tests/test_gpu_population_limits.py): padded and
-degenerate row widths, the selection threshold at 10 / 11 actions on NaN tables, real columns that tie with the
-padding, draw counters and agent ids that wrap at 2^32, and carried state that goes through the host at a padded width.
+eligibility traces (k_trace_rollout), Dyna-Q (k_dyna_rollout), Double Q (k_double_rollout), n-step Tree Backup
+(k_tree_rollout) and the two greedy-evaluation kernels -- at the places the Q-learning kernel was already taken to
+(tests/test_gpu_population_limits.py): padded and degenerate row widths, the selection threshold at 10 / 11 actions on
+NaN tables, real columns that tie with the padding, draw counters and agent ids that wrap at 2^32, and carried state
+that goes through the host at a padded width.
 
 Every comparison is bit for bit against the NumPy model run of the same run (td_rules_model.py, n_step_model.py,
-trace_model.py, dyna_model.py, double_q_model.py), through the ``_check`` of the family's own test module: tables,
-episode returns and their steps, counts, final observation / env word / running return, schedule values, draw counter
-and the family's carried state.  The single-table evaluation is compared with the standalone one-agent evaluation, as in
-test_gpu_population_eval.py.  No tolerance anywhere.  Every case asserts the build it reaches (path, rule, NV, masked).
+trace_model.py, dyna_model.py, double_q_model.py, tree_backup_model.py), through the ``_check`` of the family's own test
+module: tables, episode returns and their steps, counts, final observation / env word / running return, schedule
+values, draw counter and the family's carried state.  The single-table evaluation is compared with the standalone
+one-agent evaluation, as in test_gpu_population_eval.py.  No tolerance anywhere.  Every case asserts the build it
+reaches (path, rule, NV, masked).
 
 The inputs of the NaN and infinity cases are built here by functions without a device in them;
 tests/test_population_rule_width_cases.py asserts on the models alone that they keep enough runs to test something.
@@ -26,6 +28,8 @@ import test_gpu_dyna as dy
 import test_gpu_n_step as ns
 import test_gpu_td_rules as td
 import test_gpu_traces as tr
+import test_gpu_tree_backup as tb
+import tree_backup_cases as tbc
 from double_q_model import DoubleRun
 from dyna_model import DynaRun
 from n_step_model import NStepRun
@@ -36,6 +40,7 @@ from test_gpu_double_q import _run_flagged, special_tables
 from test_gpu_population import _schedules
 from test_gpu_population_limits import _nv
 from trace_model import TraceRun
+from tree_backup_model import TreeBackupRun
 
 pytestmark = pytest.mark.gpu
 
@@ -45,10 +50,12 @@ FIXED = (0, 1, 62, 63, 64, 65, 66)
 N_STEP, TRACE_K, PLANNING = 3, 4, 4
 COMBOS = [(np.float32, "iter"), (np.float64, "vec"), (np.float32, "vec"), (np.float64, "iter")]
 
-# a family: "<kernel>[-<rule>[-<trace kind>]]"
+# a family: "<kernel>[-<rule>[-<trace kind>]]"; Tree Backup: "tree-<horizon>"
 FAMILIES = (["sarsa", "expected_sarsa"] + [f"nstep-{rule}" for rule in ns.RULES]
             + [f"trace-{rule}-{kind}" for rule in tr.RULES for kind in tr.KINDS] + ["dyna", "double"])
 SIX = ["sarsa", "expected_sarsa", "nstep", "trace", "dyna", "double"]
+SEVEN = [*SIX, "tree"]  # appended: the six keep their indices, and with them their dtypes, learn modes and seeds
+TREE_FAMILIES = [f"tree-{n}" for n in tbc.HORIZONS]
 
 
 def _product():
@@ -56,12 +63,20 @@ def _product():
 
 
 def _rotated(family, i):
-    """The i-th member of one of the six families: n-step and the traces rotate their rules and kinds."""
+    """The i-th member of one of the seven families: n-step and the traces rotate their rules and kinds, Tree Backup
+    its horizon."""
     if family == "nstep":
         return f"nstep-{ns.RULES[i % 2]}"
     if family == "trace":
         return f"trace-{tr.RULES[i % 2]}-{tr.KINDS[(i // 2) % 2]}"
+    if family == "tree":  # (from the second horizon on: the first special-table shape then has a horizon above 2)
+        return f"tree-{tbc.HORIZONS[(i + 1) % 3]}"
     return family
+
+
+def group_of(fam):
+    """The family a width case counts for: the Tree Backup horizons are one family."""
+    return "tree" if fam.startswith("tree-") else fam
 
 
 def _sample(seed, extra=3):
@@ -87,6 +102,8 @@ def family_kw(fam, M):
         return {"update_rule": rest[0], "trace_decay": _lambdas(M), "trace_length": TRACE_K, "trace_kind": rest[1]}
     if kind == "dyna":
         return {"planning_steps": PLANNING}
+    if kind == "tree":
+        return {"tree_backup": int(rest[0])}
     return {"double_q": True}
 
 
@@ -105,6 +122,8 @@ def model_run(fam, env, r, sched, seed, dt, mode, q0=None, qb0=None):
                         q0=q0, **kw)
     if kind == "dyna":
         return DynaRun(env, gamma[r], eps_s[r], lr_s[r], n=PLANNING, q0=q0, **kw)
+    if kind == "tree":  # (with the census of its branches and of the cut rows it reads: tests/tree_backup_cases.py)
+        return tbc.with_census(TreeBackupRun(env, gamma[r], eps_s[r], lr_s[r], n=int(rest[0]), q0=q0, **kw))
     return DoubleRun(env, gamma[r], eps_s[r], lr_s[r], qa0=q0, qb0=qb0, **kw)
 
 
@@ -150,6 +169,8 @@ def reached(fam, pop, A, masked):
         tr._reached(pop, rest[0], TRACE_K, rest[1], nv=nv, masked=masked)
     elif kind == "dyna":
         dy._reached(pop, PLANNING, nv=nv, masked=masked)
+    elif kind == "tree":
+        tb._reached(pop, int(rest[0]), nv=nv, masked=masked)
     else:
         dq._reached(pop, nv=nv, masked=masked)
 
@@ -164,6 +185,8 @@ def check(fam, pop, res, r, run, history, at, snap, counter):
     kind = fam.split("-")[0]
     if kind in td.RULES:
         td._check(pop, res, r, run, history, at, snap["a"], counter)
+    elif kind == "tree":
+        tb._check(pop, res, r, run, history, at, snap["a"], counter)
     elif kind == "nstep":
         ns._check(pop, res, r, run, history, at, snap["a"], counter)
     elif kind == "trace":
@@ -174,8 +197,15 @@ def check(fam, pop, res, r, run, history, at, snap, counter):
         dq._check(pop, res, r, run, history, at, snap["a"], snap["b"], counter)
 
 
-def hash_case(fam, S, A, masked, dt, mode, runs, *, K=150, seed=0, env_seed=1, offset=0, step0=0):
-    """One call on the hash environment against the model runs ``runs``."""
+def hash_models(fam, S, A, masked, dt, mode, runs, *, K=150, seed=0, env_seed=1, offset=0, step0=0):
+    """The model's side of ``hash_case``: ``run_models`` of the runs ``runs``."""
+    return run_models(fam, lambda r: hash_model_env(r, S, A, masked, env_seed, offset), runs, K, _schedules(M_ODD), seed, dt,
+                      mode, step0=step0)
+
+
+def hash_case(fam, S, A, masked, dt, mode, runs, *, K=150, seed=0, env_seed=1, offset=0, step0=0, models=None):
+    """One call on the hash environment against the model runs ``runs`` (``models``: their ``hash_models``, if the
+    caller has them already)."""
     envs = _product()[1]
     sched = _schedules(M_ODD)
     pop = population(fam, M_ODD, S, A, sched, seed, dt, mode)
@@ -184,25 +214,42 @@ def hash_case(fam, S, A, masked, dt, mode, runs, *, K=150, seed=0, env_seed=1, o
     res = pop.run_steps(K, envs.HashTabularEnv(M_ODD, S, A, seed=env_seed, masked=masked, agent_offset=offset))
     reached(fam, pop, A, masked)
     snap = snapshot(fam, pop)
-    done, flagged = run_models(fam, lambda r: hash_model_env(r, S, A, masked, env_seed, offset), runs, K, sched, seed, dt,
-                               mode, step0=step0)
-    assert not flagged
+    done, flagged = models or hash_models(fam, S, A, masked, dt, mode, runs, K=K, seed=seed, env_seed=env_seed,
+                                          offset=offset, step0=step0)
+    assert not flagged and sorted(done) == sorted(runs)
     for r, (run, history, at) in done.items():
         check(fam, pop, res, r, run, history, at, snap, step0 + K)
     return pop, res, done
 
 
-# ---- 1. padded and degenerate row widths, all six training families ---------------------------------------------------------
+# ---- 1. padded and degenerate row widths, all seven training families -------------------------------------------------------
 WIDTHS = [1, 2, 3, 5, 9, 17, 33, 63]
 WIDTH_CASES = [pytest.param(fam, A, masked, *COMBOS[(wi + 2 * int(masked) + fi) % 4],
                             id=f"{fam}-A{A}-{'masked' if masked else 'plain'}")
                for fi, fam in enumerate(FAMILIES) for wi, A in enumerate(WIDTHS) for masked in (False, True)]
+# Tree Backup, appended: the horizon rotates with the width and the mask, and S = 40 -- at S = 300 stores into the held
+# row and cut states equal to s' are 10 to 20 times rarer
+TREE_S = 40
+WIDTH_CASES += [pytest.param(fam, A, masked, *COMBOS[(wi + 2 * int(masked) + len(FAMILIES)) % 4],
+                             id=f"{fam}-A{A}-{'masked' if masked else 'plain'}")
+                for wi, A in enumerate(WIDTHS) for masked in (False, True)
+                for fam in [TREE_FAMILIES[(wi + int(masked)) % 3]]]
+TREE_WIDTH_CASES = [p.values for p in WIDTH_CASES if group_of(p.values[0]) == "tree"]
+
+
+@functools.lru_cache(maxsize=None)
+def tree_width_models(fam, A, masked, dt, mode):
+    """The model's side of a Tree Backup width case, computed once for this module and for
+    tests/test_population_rule_width_cases.py."""
+    return hash_models(fam, TREE_S, A, masked, dt, mode, _sample(A))
 
 
 @pytest.mark.parametrize(("fam", "A", "masked", "dt", "mode"), WIDTH_CASES)
 def test_every_padded_width_matches_the_model(fam, A, masked, dt, mode):
-    S = 100 if fam == "dyna" else 300
-    _, _, done = hash_case(fam, S, A, masked, dt, mode, _sample(A))
+    tree = group_of(fam) == "tree"
+    S = 100 if fam == "dyna" else TREE_S if tree else 300
+    _, _, done = hash_case(fam, S, A, masked, dt, mode, _sample(A),
+                           models=tree_width_models(fam, A, masked, dt, mode) if tree else None)
     if A > 1:  # (at A = 1 explore and greedy coincide and every row has one candidate: the walk is a fixed cycle)
         assert any(np.any(t) for run, _, _ in done.values() for t in tables_of(run)), "no compared run learned anything"
 
@@ -218,7 +265,7 @@ def _steps(fam):
 
 
 NAN_CASES = [pytest.param(family, A, masked, id=f"{family}-A{A}-{'masked' if masked else 'plain'}")
-             for family in SIX for A, masked in NAN_SHAPES]
+             for family in SEVEN for A, masked in NAN_SHAPES]
 
 
 @functools.lru_cache(maxsize=None)
@@ -226,7 +273,7 @@ def nan_case(family, A, masked):
     """The inputs and the model's side of one case: a dict of fam, dt, mode, sched, q0, qb0, done and flagged."""
     i = NAN_SHAPES.index((A, masked))
     fam = _rotated(family, i)
-    dt, mode = COMBOS[(i + SIX.index(family)) % 4]
+    dt, mode = COMBOS[(i + SEVEN.index(family)) % 4]
     sched = _schedules(M_ODD)
     q0, qb0 = dq.special_case("both", A, dt, S=NAN_S) if fam == "double" else (special_tables(M_ODD, NAN_S, A, dt, seed=A), None)
     done, flagged = run_models(fam, lambda r: hash_model_env(r, NAN_S, A, masked), range(M_ODD), _steps(fam), sched, 0, dt,
@@ -257,7 +304,7 @@ def test_the_selection_threshold_on_special_tables_matches_the_model(family, A, 
 
 
 # ---- 3. real columns that tie with the padding ---------------------------------------------------------------------------------
-TIE_FAMILIES = ["sarsa", "expected_sarsa", "dyna", "double"]
+TIE_FAMILIES = ["sarsa", "expected_sarsa", "dyna", "double", "tree-3"]
 TIE_CASES = [pytest.param(fam, A, id=f"{fam}-A{A}") for fam in TIE_FAMILIES for A in (3, 5)]
 
 
@@ -302,6 +349,8 @@ def test_real_columns_that_tie_with_the_padding_keep_the_pick_inside_the_row(fam
     if fam == "sarsa":  # the pick made last, for the next step, lies inside the row (a flagged run may hold none: -1)
         pending = res.state_dict["pending_actions"]
         assert (pending < A).all() and (pending[list(c["done"])] >= 0).all()
+    if group_of(fam) == "tree":  # ... and so does every action a completed run holds in its window
+        assert (res.state_dict["tree_backup_window"]["actions"][list(c["done"])] < A).all()
     # a pick at or above A would store into a padding column and leave the real cell as it was: the real columns of
     # every compared run equal the model's (above), and the runs differ from their start
     assert not np.array_equal(pop.q_tables, c["q0"], equal_nan=True)
@@ -311,24 +360,24 @@ def test_real_columns_that_tie_with_the_padding_keep_the_pick_inside_the_row(fam
 STEP0 = 2**32 - 70   # a 150-step call: the step whose successor counter is exactly 2^32 is step 69 of the call
 OFFSET = 2**32 - 30  # run r has agent id (OFFSET + r) mod 2^32: 2^32 - 30 .. 36
 WRAP_SHAPE = {"sarsa": (9, True), "expected_sarsa": (5, False), "nstep": (17, True), "trace": (3, False), "dyna": (5, True),
-              "double": (9, False)}
+              "double": (9, False), "tree": (33, True)}  # Tree Backup: a 64-bit lane mask
 
 
-@pytest.mark.parametrize("family", SIX)
+@pytest.mark.parametrize("family", SEVEN)
 def test_a_step_counter_crossing_2_pow_32_matches_the_model(family):
-    i = SIX.index(family)
+    i = SEVEN.index(family)
     A, masked = WRAP_SHAPE[family]
     _, res, done = hash_case(_rotated(family, i), 200, A, masked, *COMBOS[i % 4], _sample(i), step0=STEP0)
     assert res.state_dict["rng_step"] == STEP0 + 150 > 2**32
 
 
-@pytest.mark.parametrize("family", SIX)
+@pytest.mark.parametrize("family", SEVEN)
 def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_model(family, tmp_path):
     """Two calls of 75 steps; the second by a fresh population from the saved tables (Dyna-Q: and model) and the pickled
     state dict.  The wrap is step 69 of the first call: the pending action, window, slots or model cross the boundary
     five steps after it."""
     envs = _product()[1]
-    i = SIX.index(family)
+    i = SEVEN.index(family)
     fam = _rotated(family, i + 1)
     A, masked = WRAP_SHAPE[family]
     dt, mode = COMBOS[(i + 1) % 4]
@@ -352,6 +401,10 @@ def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_m
     if fam == "dyna":
         fresh.load_model(tmp_path / "model.npz")
     fresh.restore_training_state(sd)
+    if family == "tree":  # the window carries entries from before the wrap through the pickle
+        window = first.state_dict["tree_backup_window"]
+        assert window["length"].max() == pop.tree_backup - 1, "the window must be non-empty at the cut"
+        tb._same_window(fresh.tree_backup_window, window)
     second = fresh.run_steps(K, env(), sd)
     snap2 = snapshot(fam, fresh)
     for p in (pop, fresh):
@@ -366,7 +419,7 @@ def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_m
         check(fam, fresh, second, r, run, history, at, snap2, STEP0 + 2 * K)
 
 
-@pytest.mark.parametrize("family", ["trace", "dyna"])
+@pytest.mark.parametrize("family", ["trace", "dyna", "tree"])
 def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(family):
     """The table environment hashes the step too (``step >> 32`` in its word), unlike the hash environment."""
     from dist_classicrl_amd.environments.device_envs import encode_table_mdp
@@ -374,8 +427,8 @@ def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(famil
     envs = _product()[1]
     arrays, isd, masks = random_mdp(300, 9, 3, seed=6, masked=True)
     mdp = encode_table_mdp(*arrays, isd, masks)
-    fam = _rotated(family, 0)
-    dt, mode = COMBOS[1 if family == "trace" else 2]
+    fam = _rotated(family, 0)  # (Tree Backup: n = 5)
+    dt, mode = COMBOS[{"trace": 1, "dyna": 2, "tree": 3}[family]]
     S, A, K, seed = 300, 9, 150, 2
     sched = _schedules(M_ODD)
     pop = population(fam, M_ODD, S, A, sched, seed, dt, mode)
@@ -391,10 +444,10 @@ def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(famil
     assert res.episode_counts.sum() > 0
 
 
-@pytest.mark.parametrize("family", SIX)
+@pytest.mark.parametrize("family", SEVEN)
 def test_agent_ids_that_wrap_past_2_pow_32_match_the_model(family):
-    i = SIX.index(family)
-    A, masked = WRAP_SHAPE[SIX[(i + 3) % 6]]
+    i = SEVEN.index(family)
+    A, masked = WRAP_SHAPE[family if family == "tree" else SIX[(i + 3) % 6]]  # (the six trade shapes among themselves)
     runs = sorted(set(_sample(30 + i)) | {28, 29, 30, 31})  # ids 2^32 - 2, 2^32 - 1, 0 and 1
     hash_case(_rotated(family, i + 2), 200, A, masked, *COMBOS[(i + 2) % 4], runs, offset=OFFSET)
 
@@ -483,12 +536,12 @@ def test_a_full_dyna_model_through_the_getter_and_the_setter_at_a_padded_width(S
 
 
 @pytest.mark.parametrize("masked", [False, True])
-@pytest.mark.parametrize("family", ["trace", "nstep"])
+@pytest.mark.parametrize("family", ["trace", "nstep", "tree"])
 def test_slots_and_windows_through_the_getter_and_the_setter_at_five_actions(family, masked):
     envs = _product()[1]
-    key, attr = {"trace": ("eligibility_traces", "eligibility_traces"), "nstep": ("n_step_window", "n_step_window")}[family]
-    i = int(masked) + 2 * (family == "nstep")
-    fam = _rotated(family, i)
+    key = attr = {"trace": "eligibility_traces", "nstep": "n_step_window", "tree": "tree_backup_window"}[family]
+    i = 1 - int(masked) if family == "tree" else int(masked) + 2 * (family == "nstep")
+    fam = "tree-5" if family == "tree" else _rotated(family, i)
     dt, mode = COMBOS[i]
     M, S, A, K1, K2, seed = M_ODD, 12, 5, 80, 70, 6
     sched = _schedules(M)
@@ -504,6 +557,11 @@ def test_slots_and_windows_through_the_getter_and_the_setter_at_five_actions(fam
     carried = getattr(pop, attr)
     busy = carried["values"] != 0 if family == "trace" else carried["length"] > 0
     assert busy.any(), "nothing is carried at the cut"
+    if family == "tree":
+        assert sorted(carried) == sorted(tb.WINDOW_KEYS)
+        held = np.arange(carried["greedy"].shape[1])[None, :] < carried["length"][:, None]
+        assert ((carried["greedy"].astype(bool) & held).any(axis=1) & (~carried["greedy"].astype(bool) & held).any(axis=1)).any(), \
+            "no window holds both a set and a cleared flag at the cut"
     for k2, value in first.state_dict[key].items():
         assert np.array_equal(carried[k2], value), k2
     fresh = population(fam, M, S, A, sched, seed, dt, mode)

@@ -201,6 +201,69 @@ def test_a_reset_drops_the_window_and_evaluation_and_train_leave_it_alone():
     assert dropped, "no segment started over a non-empty window"
 
 
+# ---- 2b. launch chopping ---------------------------------------------------------------------------------------------------
+def _same_state(a, b):
+    assert sorted(a) == sorted(b)
+    for key, value in b.items():
+        if isinstance(value, np.ndarray):
+            assert np.array_equal(a[key], value), key
+    _same_window(a["tree_backup_window"], b["tree_backup_window"])
+
+
+def test_a_logged_call_cut_into_launches_equals_the_unlogged_call_and_the_model():
+    """Every launch loads the window from the per-run arrays and stores it there, compacted to ``base = 0``."""
+    from test_gpu_population_limits import _cycled_schedules
+
+    envs = _product()[1]
+    M, K, S, A, n = 20_000, 2000, 40, 8, 4
+    sched = _cycled_schedules(M)
+
+    def make():
+        return _population(M, S, A, sched, 21, np.float32, "iter", n)
+
+    def env():
+        return envs.HashTabularEnv(M, S, A, seed=1, masked=True)
+
+    logged = make()
+    res = logged.run_steps(K, env())
+    _reached(logged, n, nv=2, masked=True)
+    # 2^23 log entries / 20 000 runs = 419 steps per launch: 5 launches, each with its scan and its pack
+    assert logged.last_stats["launches"] == 15
+    tables = logged.q_tables
+    quiet = make()
+    res_q = quiet.run_steps(K, env(), log=False)
+    assert 1 < quiet.last_stats["launches"] < 5, "the unlogged call is cut differently"
+    assert np.array_equal(quiet.q_tables, tables)
+    assert np.array_equal(res_q.episode_counts, res.episode_counts)
+    assert np.array_equal(res_q.mean_returns, res.mean_returns, equal_nan=True)
+    _same_state(res_q.state_dict, res.state_dict)
+    _same_window(quiet.tree_backup_window, res.state_dict["tree_backup_window"])
+    del quiet
+    halves = make()
+    e = env()
+    first = halves.run_steps(K // 2, e)
+    second = halves.run_steps(K // 2, e, first.state_dict)
+    assert first.state_dict["tree_backup_window"]["length"].max() == n - 1
+    assert np.array_equal(halves.q_tables, tables)
+    assert np.array_equal(first.episode_counts + second.episode_counts, res.episode_counts)
+    # the mean of a call is the float32 sequential sum of its logged returns over their count: the two calls' logs,
+    # joined run by run, are the one call's log, and with it its means
+    at1, at2 = first.offsets, second.offsets
+    for r in range(M):
+        joined = np.concatenate([first.returns[at1[r]:at1[r + 1]], second.returns[at2[r]:at2[r + 1]]])
+        assert np.array_equal(joined, res.returns[res.offsets[r]:res.offsets[r + 1]]), r
+        if joined.size:
+            assert np.cumsum(joined, dtype=np.float32)[-1] / np.float32(joined.size) == res.mean_returns[r], r
+    _same_state(second.state_dict, res.state_dict)
+    _same_window(halves.tree_backup_window, res.state_dict["tree_backup_window"])
+    del halves
+    p = {"S": S, "A": A, "seed": 1, "masked": True}
+    picked = [0, 1, 63, 64, 65, 1023, 1024, 1025, 10_000, M - 1]
+    for r, run in tc.model_runs("hash", p, picked, n, sched, 21, np.float32, "iter").items():
+        history, at = run.run(K)
+        _check(logged, res, r, run, history, at, {r: tables[r]}, K)
+
+
 # ---- 3. NaN, infinities and ties in the tables; runs without a selectable action -----------------------------------------
 @pytest.mark.parametrize(("A", "masked", "dt", "mode"), [
     (8, False, np.float32, "iter"),   # list selection: steps over NaN

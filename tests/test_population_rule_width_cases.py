@@ -10,12 +10,23 @@ case is built here by the very functions the GPU module calls (``nan_case``, ``t
 * at least one completed run ends with a non-finite cell;
 * the -inf-row cases: at least one completed run has written into its -inf row.
 
+Tree Backup (``tree_backup_model.py``) has conditions of its own, counted by ``tree_backup_cases.with_census``:
+
+* the width cases of one horizon together perform every kind of update in ``tree_backup_cases.required``, and every
+  case with more than one action performs an update with a cut and one without;
+* the width cases of horizons 5 and 16 together reach all four sources of the value at the cut
+  (``tree_backup_cases.BRANCHES``), those of horizon 2 all but the cut among the old entries, which it cannot have;
+* over the masked threshold cases, some update reads a cut row whose NaN sits in masked-out columns only and some
+  update reads one with a NaN in a valid column -- and some of either through the kernel's own walk of a row
+  (``row_np_max_at``), which a horizon of 2 never takes.
+
 Every test prints the figures it asserts on (``pytest -s``).
 """
 import numpy as np
 import pytest
 
 import test_gpu_population_rule_widths as cases
+import tree_backup_cases as tbc
 
 HALF = (cases.M_ODD + 1) // 2
 
@@ -80,6 +91,72 @@ def test_every_family_meets_every_dtype_and_learn_mode_in_the_width_sweep():
     met = {}
     for p in cases.WIDTH_CASES:
         fam, _, _, dt, mode = p.values
-        met.setdefault(fam, set()).add((dt, mode))
-    assert sorted(met) == sorted(cases.FAMILIES)
+        met.setdefault(cases.group_of(fam), set()).add((dt, mode))
+    assert sorted(met) == sorted([*cases.FAMILIES, "tree"])
     assert all(len(v) == 4 for v in met.values()), met
+    tree = cases.TREE_WIDTH_CASES
+    assert [(A, masked) for _, A, masked, _, _ in tree] == [(A, masked) for A in cases.WIDTHS for masked in (False, True)]
+    for fam, A, masked, _, _ in tree:
+        assert fam == f"tree-{tbc.HORIZONS[(cases.WIDTHS.index(A) + int(masked)) % 3]}", (fam, A, masked)
+    # the ids, dtypes and learn modes of the other families' cases are those they had before Tree Backup was appended
+    assert [p.id for p in cases.WIDTH_CASES[:3]] == ["sarsa-A1-plain", "sarsa-A1-masked", "sarsa-A2-plain"]
+    assert cases.WIDTH_CASES[len(cases.FAMILIES) * 16 - 1].id == "double-A63-masked"
+    assert len(cases.WIDTH_CASES) == (len(cases.FAMILIES) + 1) * 16
+
+
+def _tree_totals(which, cases_of_horizon):
+    """The sum over the compared runs of the given Tree Backup width cases of the counter ``which`` of every run."""
+    total = {}
+    for case in cases_of_horizon:
+        done, flagged = cases.tree_width_models(*case)
+        assert not flagged
+        for run, _, _ in done.values():
+            for kind, count in getattr(run, which).items():
+                total[kind] = total.get(kind, 0) + int(count)
+    return total
+
+
+@pytest.mark.parametrize("n", tbc.HORIZONS)
+def test_the_tree_backup_width_cases_of_a_horizon_perform_every_kind_of_update(n):
+    of_n = [c for c in cases.TREE_WIDTH_CASES if c[0] == f"tree-{n}"]
+    assert len(of_n) >= 5 and {c[2] for c in of_n} == {False, True}
+    got = _tree_totals("counts", of_n)
+    print(f"tree-{n}: {len(of_n)} width cases perform {got}")
+    missing = sorted(kind for kind in tbc.required({"n": n, "kind": "hash"}) if not got[kind])
+    assert not missing, (missing, got)
+    for case in of_n:
+        one = _tree_totals("counts", [case])
+        cut = one["steady_cut_next"] + one["steady_cut_deep"] + one["flush_cut"]
+        plain = one["steady_no_cut"] + one["flush_no_cut"]
+        print(f"  A={case[1]} masked={case[2]}: updates with a cut {cut}, without {plain}, {one}")
+        if case[1] == 1:  # one action: every pick is greedy, and the walk is a fixed cycle
+            assert cut == 0 and plain > 0
+        else:
+            assert cut > 0 and plain > 0, case
+
+
+def test_the_tree_backup_width_cases_reach_every_source_of_the_value_at_the_cut():
+    long = _tree_totals("branches", [c for c in cases.TREE_WIDTH_CASES if c[0] != "tree-2"])
+    short = _tree_totals("branches", [c for c in cases.TREE_WIDTH_CASES if c[0] == "tree-2"])
+    print(f"horizons 5 and 16: {long}\nhorizon 2: {short}")
+    assert sorted(long) == sorted(short) == sorted(tbc.BRANCHES)
+    assert all(long.values()), long
+    assert short["steady_cut_old"] == 0  # a window of one old entry has none after entry 0
+    assert all(count for kind, count in short.items() if kind != "steady_cut_old"), short
+
+
+def test_the_masked_tree_backup_threshold_cases_read_cut_rows_with_hidden_and_with_valid_nans():
+    total = dict.fromkeys(tbc.CUT_ROWS, 0)
+    for A, masked in cases.NAN_SHAPES:
+        c = cases.nan_case("tree", A, masked)
+        got = dict.fromkeys(tbc.CUT_ROWS, 0)
+        for run, _, _ in c["done"].values():
+            for kind, count in run.cut_rows.items():
+                got[kind] += count
+        print(f"{c['fam']} A={A} masked={masked}: cut rows read by completed runs {got}")
+        if masked:
+            for kind, count in got.items():
+                total[kind] += count
+        else:
+            assert not any(got.values())  # (no column is masked out, and the census counts masked rows only)
+    assert all(total.values()), total

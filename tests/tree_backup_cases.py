@@ -132,6 +132,58 @@ def performed(case_id):
     return total
 
 
+BRANCHES = ("steady_cut_old", "steady_cut_own", "flush_first_full", "flush_first_short")
+CUT_ROWS = ("nan_hidden", "nan_valid", "gathered_nan_hidden", "gathered_nan_valid")
+
+
+def with_census(run):
+    """``run`` with two counters of its own, filled as it runs, read from the model's windows (``KINDS`` stay as they are).
+
+    ``run.branches``: the sources the kernel's step has for the value at the cut, which ``KINDS`` do not tell apart --
+    ``steady_cut_old``: a steady update whose nearest cut lies among the entries the step started with (the row gathered
+    at the top of the step); ``steady_cut_own``: one whose cut is the step's own entry, ``cut == L - 1`` (the held row's
+    maximum); ``flush_first_full`` / ``flush_first_short``: the first update of a terminated step with ``L == n`` (the
+    early path inside a flush) / ``L < n`` (the per-entry path for entry 0).
+
+    ``run.cut_rows``: the reads of a cut row (every ``_row_max`` of a step after its first, which is the flag's) with a
+    NaN in masked-out columns only (``nan_hidden``: the maximum stays a number) and with one in a valid column
+    (``nan_valid``: the fold carries NaN); ``gathered_...``: those of them that the kernel reads from the table
+    (``row_np_max_at``), which is every cut but the one at the step's own entry seen from entry 0 of a full window, whose
+    row is the held row.  With ``n = 2`` no cut row is ever gathered."""
+    rt = run.rt
+    run.branches = dict.fromkeys(BRANCHES, 0)
+    run.cut_rows = dict.fromkeys(CUT_ROWS, 0)
+    count, row_max, step = rt._count, rt._row_max, rt.run_single_step
+    calls, last = [0], [None]
+
+    def counted(j, L, cut, start, terminated, s_j, n_obs):
+        if last[0] is not None and not (j == 0 and L == rt.n and cut == L - 1):
+            run.cut_rows["gathered_" + last[0]] += 1
+        last[0] = None
+        if terminated:
+            if j == 0:
+                run.branches["flush_first_full" if L == rt.n else "flush_first_short"] += 1
+        elif cut is not None:
+            run.branches["steady_cut_own" if cut == L - 1 else "steady_cut_old"] += 1
+        return count(j, L, cut, start, terminated, s_j, n_obs)
+
+    def read(s, mask):
+        calls[0] += 1
+        if calls[0] > 1 and mask is not None:
+            nan = np.isnan(rt.algorithm.q_table[s])
+            last[0] = "nan_valid" if nan[np.where(mask)].any() else "nan_hidden" if nan.any() else None
+            if last[0] is not None:
+                run.cut_rows[last[0]] += 1
+        return row_max(s, mask)
+
+    def one_step(*args):
+        calls[0] = 0
+        return step(*args)
+
+    rt._count, rt._row_max, rt.run_single_step = counted, read, one_step
+    return run
+
+
 def special_tables(M, S, A, dt, seed):
     """The NaN / infinity tables of tests/test_gpu_td_rules.py, and in every run r two TIE rows: row ``r % S`` all equal,
     row ``(r + 1) % S`` with its first two columns equal and above the rest."""
