@@ -38,6 +38,11 @@ N_STEP_MAX = 16  # qe_population_set_n_step
 TREE_BACKUP_MAX = 16  # qe_population_set_tree_backup
 TRACE_MAX = 32  # qe_population_set_traces
 PLANNING_MAX = 64  # qe_population_set_planning
+QUEUE_MAX = 32  # qe_population_set_sweeping
+PLANNING_ORDERS = ("uniform", "prioritized")
+# qe_population_set_sweeping: the (table dtype, 16-byte loads per fp32 row) builds of k_sweep_rollout that are NOT compiled
+# because they do not fit the register file without scratch (sweep_supported in csrc/qe_host.h)
+SWEEP_REFUSED = frozenset()
 # qe_population_set_visits: the (table dtype, 16-byte loads per fp32 row) builds of k_visit_rollout that are NOT compiled
 # because they do not fit the register file without scratch (visit_supported in csrc/qe_host.h)
 VISIT_REFUSED = frozenset()
@@ -58,7 +63,9 @@ def decode_variant(v: int) -> dict:
     ``k_trace_rollout``) is the population with eligibility traces: the rule in bits 4-5 (0 = Q-learning, Watkins's
     Q(lambda); 1 = SARSA(lambda)), ``trace_length`` in bits 24-29 and ``trace_kind`` in bit 30 (0 and None on every other
     path).  Path 13 (``population_dyna``, kernel ``k_dyna_rollout``) is the Q-learning population with Dyna-Q: NV and
-    masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has.  Path 14
+    masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has; with bit 4 set the
+    planning order is prioritized sweeping (kernel ``k_sweep_rollout``) and the dict gains ``prioritized`` (True) and
+    ``queue_length`` (bits 5-9 plus 1), two keys that no other dict has.  Path 14
     (``population_visit``, kernel ``k_visit_rollout``) is the Q-learning population with visit counts: NV and masked as path
     6, ``visit_lr`` in bit 4 and ``bonus`` (some run's beta is above 0) in bit 5, two keys that only this path's dict has.
     Path 15 (``population_tree``, kernel ``k_tree_rollout``) is the Q-learning population with n-step Tree Backup: NV and
@@ -83,6 +90,9 @@ def decode_variant(v: int) -> dict:
     }
     if (v & 15) == 13:
         out["planning_steps"] = (v >> 24) & 127
+        if (v >> 4) & 1:
+            out["prioritized"] = True
+            out["queue_length"] = ((v >> 5) & 31) + 1
     if (v & 15) == 14:
         out["visit_lr"] = bool((v >> 4) & 1)
         out["bonus"] = bool((v >> 5) & 1)
@@ -95,6 +105,12 @@ def visit_build_shipped(dtype, action_size: int) -> bool:
     """Whether ``k_visit_rollout`` is built for rows of ``action_size`` actions of ``dtype`` (``VISIT_REFUSED``)."""
     nv = max(4, 1 << (int(action_size) - 1).bit_length()) // 4
     return (np.dtype(dtype).name, nv) not in VISIT_REFUSED
+
+
+def sweep_build_shipped(dtype, action_size: int) -> bool:
+    """Whether ``k_sweep_rollout`` is built for rows of ``action_size`` actions of ``dtype`` (``SWEEP_REFUSED``)."""
+    nv = max(4, 1 << (int(action_size) - 1).bit_length()) // 4
+    return (np.dtype(dtype).name, nv) not in SWEEP_REFUSED
 
 
 def variant_symbol(v: int, dtype: str = "float", env: str = "HashEnv", lanes_per_row: int = 4, vec: bool = False) -> str:
@@ -263,6 +279,12 @@ PROTOTYPES = {
     "qe_population_planning": (C.c_int, [_P]),
     "qe_population_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
     "qe_population_set_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
+    "qe_population_set_sweeping": (C.c_int, [_P, C.c_int32, _F64P]),
+    "qe_population_sweeping": (C.c_int, [_P]),
+    "qe_population_predecessors": (C.c_int, [_P, _I32P, _I32P]),
+    "qe_population_set_predecessors": (C.c_int, [_P, _I32P, _I32P]),
+    "qe_population_queue": (C.c_int, [_P, _I32P, _F64P]),
+    "qe_population_set_queue": (C.c_int, [_P, _I32P, _F64P]),
     "qe_population_set_visits": (C.c_int, [_P, _F64P, C.c_int32]),
     "qe_population_visits": (C.c_int, [_P, _I32P, _I32P, _F64P]),
     "qe_population_visit_counts": (C.c_int, [_P, _U32P]),

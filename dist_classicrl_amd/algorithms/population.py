@@ -68,6 +68,19 @@ it is NOT in the state dict.  :attr:`planning_model` reads and sets it, ``save_m
 schedules), then passes the state dict to ``run_steps``.  ``double_q=True``, ``n_step > 1`` and ``trace_decay`` are
 refused with planning.  DESIGN section 4.3c defines the step; ``tests/dyna_model.py`` restates it on the oracle.
 
+``planning_order="prioritized"`` (with ``planning_steps=n``; kernel ``k_sweep_rollout``) replaces the uniform draws of
+Dyna-Q by prioritized sweeping (Moore & Atkeson 1993; Sutton & Barto 8.4): the ``n`` updates go where the table is about
+to change.  Every run keeps the predecessors of every state (the cells its model leads there from) and a queue of
+``queue_length`` cells; when an update changes a cell by more than ``sweep_threshold`` (one value or one per run: a grid
+axis), the predecessors of its state whose own update would change by more than the threshold enter the queue with that
+size as priority, and planning pops the largest first and stops early when the queue is empty.  No draw is consumed and
+every operation is a compare, an ``abs`` or the update itself, so the runs equal a NumPy model bit for bit.  The
+predecessor lists are knowledge and travel with the model (``planning_model`` gains ``pred_head`` and ``pred_next``;
+a model saved by a Dyna-Q population loads, its lists are rebuilt); the queue is run state:
+``state_dict["sweep_queue"]`` carries it from call to call, :attr:`sweep_queue` reads and sets it.  A fresh process
+resumes with ``load``, ``load_model`` and ``restore_training_state``, in that order.  Everything Dyna-Q refuses is refused
+here too.  DESIGN section 4.3c defines the step; ``tests/sweep_model.py`` restates it on the oracle.
+
 ``exploration_bonus=beta`` (one beta >= 0 or one per run) and ``visit_lr=True`` (Q-learning only; kernel
 ``k_visit_rollout``) turn on per-cell visit counts ``N(s, a)``, the directed-exploration lever next to epsilon.  The pick
 sees ``Q[s, :] + beta / sqrt(N[s, :])`` instead of the Q-row (count-based optimism, MBIE-EB: an untried action has an
@@ -225,6 +238,16 @@ def _model_specs(runs, state_size, action_size):
             ("visited", (runs, state_size * action_size), "iu", np.int32), ("count", (runs,), "iu", np.int32))
 
 
+def _sweep_model_specs(runs, state_size, action_size):
+    return (*_model_specs(runs, state_size, action_size), ("pred_head", (runs, state_size), "iu", np.int32),
+            ("pred_next", (runs, state_size, action_size), "iu", np.int32))
+
+
+def _queue_specs(runs, queue_length):
+    slots = (runs, queue_length)
+    return ("cells", slots, "iu", np.int32), ("priorities", slots, "fiu", np.float64)
+
+
 def _spec_arrays(what, value, specs, exact=False) -> tuple | None:
     """The dict ``value`` (``what`` names it) as the tuple of contiguous arrays ``specs`` describes; None for None and
     ``ValueError`` on anything else.  ``exact``: no cast may change a value -- a float must be exact in the target dtype
@@ -286,6 +309,23 @@ def model_arrays(model, runs, state_size, action_size) -> tuple | None:
     return _spec_arrays("planning_model", model, _model_specs(runs, state_size, action_size), exact=True)
 
 
+def sweep_model_arrays(model, runs, state_size, action_size) -> tuple | None:
+    """A ``planning_model`` of a population with ``planning_order="prioritized"`` as the arrays the library takes: those
+    of :func:`model_arrays` and, from the 7-key dict, ``pred_head`` (int32 ``[runs, S]``) and ``pred_next`` (int32
+    ``[runs, S, A]``).  The 5-key dict of a Dyna-Q population gives the five arrays alone (the library then rebuilds the
+    lists in their canonical order); ``ValueError`` on anything else.  Whether the lists fit the model is the library's
+    check."""
+    if isinstance(model, dict) and len(model) == 5:
+        return model_arrays(model, runs, state_size, action_size)
+    return _spec_arrays("planning_model", model, _sweep_model_specs(runs, state_size, action_size), exact=True)
+
+
+def queue_arrays(queue, runs, queue_length) -> tuple | None:
+    """``sweep_queue`` of a state dict as the ``(cells, priorities)`` arrays the library takes (None: every queue empty):
+    int32 ``[runs, queue_length]`` and float64 ``[runs, queue_length]``; ``ValueError`` on anything else."""
+    return _spec_arrays("sweep_queue", queue, _queue_specs(runs, queue_length), exact=True)
+
+
 def visit_count_array(counts, runs, state_size, action_size) -> np.ndarray | None:
     """``visit_counts`` as the uint32 ``[runs, S, A]`` array the library takes (None: every count zero): integers in
     ``[0, 2^32)`` of exactly that shape; ``ValueError`` on anything else."""
@@ -306,7 +346,8 @@ def visit_count_array(counts, runs, state_size, action_size) -> np.ndarray | Non
 # population's property, and whether a population carries it.  (The planning model is knowledge, not such state.)
 _CARRIED = {"pending_actions": lambda pop: pop.update_rule == "sarsa", "n_step_window": lambda pop: pop.n_step > 1,
             "eligibility_traces": lambda pop: pop.trace_decay is not None,
-            "tree_backup_window": lambda pop: pop.tree_backup > 1}
+            "tree_backup_window": lambda pop: pop.tree_backup > 1,
+            "sweep_queue": lambda pop: pop.planning_order == "prioritized"}
 
 
 def _check_int(name, value, lo, hi) -> None:
@@ -334,7 +375,11 @@ class QLearningPopulation:
     ``trace_decay`` (None: no traces; else one lambda in [0, 1] or a sequence of ``runs``) turns on eligibility traces for
     "sarsa" and "q_learning", with ``trace_length`` slots per run (1 .. 32) of ``trace_kind`` "replacing" or
     "accumulating".  ``planning_steps`` (0: none; 1 .. 64) turns on Dyna-Q for "q_learning": that many planning updates
-    from the run's learned model after every step (:attr:`planning_model`).  ``exploration_bonus`` (None: none; else one
+    from the run's learned model after every step (:attr:`planning_model`).  ``planning_order`` is "uniform" (the default:
+    the updates replay cells drawn uniformly from the seen ones) or "prioritized" (prioritized sweeping: the updates go to
+    the cells whose value is about to change, taken from a queue of ``queue_length`` slots per run, 1 .. 32, that the
+    predecessors of every changed state enter when their increment would exceed ``sweep_threshold`` -- one finite number
+    >= 0 or a sequence of ``runs``; :attr:`sweep_queue`); it needs ``planning_steps >= 1``.  ``exploration_bonus`` (None: none; else one
     finite beta >= 0 or a sequence of ``runs``) adds ``beta / sqrt(N(s, a))`` to the row the pick sees and ``visit_lr=True``
     divides the learning rate by ``N(s, a)``; either turns on the visit counts (:attr:`visit_counts`), for "q_learning"
     without ``double_q``, ``n_step``, ``trace_decay`` or ``planning_steps``.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
@@ -343,7 +388,8 @@ class QLearningPopulation:
     def __init__(self, runs, state_size, action_size, discount_factor=0.97, lr_schedule=None,
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
                  update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
-                 trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False, tree_backup=1):
+                 trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False, tree_backup=1,
+                 planning_order="uniform", sweep_threshold=0.0, queue_length=16):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -411,6 +457,34 @@ class QLearningPopulation:
             if self.state_size * self.action_size >= 2 ** 31:
                 msg = f"planning_steps={planning_steps}: state_size * action_size must be below 2^31"
                 raise ValueError(msg)
+        if not isinstance(planning_order, str) or planning_order not in _lib.PLANNING_ORDERS:
+            msg = f"planning_order must be one of {', '.join(map(repr, _lib.PLANNING_ORDERS))}, got {planning_order!r}"
+            raise ValueError(msg)
+        self.sweep_threshold = None
+        self.queue_length = 0
+        if planning_order == "prioritized":
+            if planning_steps < 1:
+                msg = "planning_order='prioritized' orders the planning updates: it needs planning_steps >= 1"
+                raise ValueError(msg)
+            _check_int("queue_length", queue_length, 1, _lib.QUEUE_MAX)
+            try:
+                theta = np.ascontiguousarray(_per_run(sweep_threshold, self.runs, "sweep_threshold"), dtype=np.float64)
+            except (TypeError, ValueError) as err:
+                if "one entry per run" in str(err):
+                    raise
+                msg = f"sweep_threshold must be a finite number >= 0 or a sequence of {self.runs}, got {sweep_threshold!r}"
+                raise ValueError(msg) from err
+            if (theta.shape != (self.runs,) or isinstance(sweep_threshold, (bool, np.bool_))
+                    or not (np.isfinite(theta) & (theta >= 0)).all()):
+                msg = f"sweep_threshold: every threshold must be a finite number >= 0, got {sweep_threshold!r}"
+                raise ValueError(msg)
+            if not _lib.sweep_build_shipped(self.dtype, self.action_size):
+                msg = (f"prioritized sweeping: the kernel for {self.dtype} rows of {self.action_size} actions is not built (it "
+                       "does not fit the register file)")
+                raise ValueError(msg)
+            self.sweep_threshold = theta
+            self.queue_length = int(queue_length)
+        self.planning_order = planning_order
         if not isinstance(visit_lr, (bool, np.bool_)):
             msg = f"visit_lr must be a bool, got {visit_lr!r}"
             raise ValueError(msg)
@@ -520,6 +594,8 @@ class QLearningPopulation:
                                                           _lib.ptr(self.trace_decay, C.c_double)))
         if self.planning_steps:
             _lib.check(self._lib.qe_population_set_planning(self._h, self.planning_steps))
+        if self.planning_order == "prioritized":
+            _lib.check(self._lib.qe_population_set_sweeping(self._h, self.queue_length, _lib.ptr(self.sweep_threshold, C.c_double)))
         if self.counting:
             _lib.check(self._lib.qe_population_set_visits(self._h, _lib.ptr(self.exploration_bonus, C.c_double),
                                                          1 if self.visit_lr else 0))
@@ -652,11 +728,24 @@ class QLearningPopulation:
         outcome of every cell --, ``visited`` (int32 ``[runs, S * A]``: the seen cells ``s * A + a`` in order of first
         observation, -1 past the count) and ``count`` (int32 ``[runs]``).  Without planning: None.  Setting None forgets
         everything; a dict whose list names an unseen, repeated or out-of-range cell, or whose count differs from the
-        number of seen cells, is a ``ValueError``."""
+        number of seen cells, is a ``ValueError``.
+
+        ``planning_order="prioritized"`` adds the predecessor lists the kernel walks: ``pred_head`` (int32 ``[runs, S]``:
+        the cell ``s * A + a`` at the head of each state's list, -1 for an empty list) and ``pred_next`` (int32
+        ``[runs, S, A]``: the next cell of the same list; -1 at the tail and at a cell that is not linked).  The list of a
+        state holds the seen cells that lead to it without ending the episode, most recently linked first.  The setter
+        takes the 7-key dict -- lists that do not fit the model (a node that is out of range, unseen, terminated, of
+        another next state or reached twice, a seen cell left out, an unlinked cell not at -1) are a ``ValueError`` and
+        change nothing -- or the 5-key dict of a Dyna-Q population, whose lists are rebuilt in the canonical order: the seen
+        cells that are not terminated linked in visited-list order, each at the head of its next state's list.  Setting
+        or forgetting the model empties every run's :attr:`sweep_queue`."""
         if not self.planning_steps:
             return None
         model = self._state_dict_of(self._lib.qe_population_model, _model_specs(self.runs, self.state_size, self.action_size))
         model["terminated"] = model["terminated"].astype(bool)
+        if self.planning_order == "prioritized":
+            specs = _sweep_model_specs(self.runs, self.state_size, self.action_size)[5:]
+            model.update(self._state_dict_of(self._lib.qe_population_predecessors, specs))
         return model
 
     @planning_model.setter
@@ -666,7 +755,40 @@ class QLearningPopulation:
                 msg = "a population without planning_steps has no planning model"
                 raise ValueError(msg)
             return
-        self._set_state(self._lib.qe_population_set_model, model_arrays(model, self.runs, self.state_size, self.action_size), 5)
+        if self.planning_order != "prioritized":
+            self._set_state(self._lib.qe_population_set_model, model_arrays(model, self.runs, self.state_size, self.action_size), 5)
+            return
+        arrays = sweep_model_arrays(model, self.runs, self.state_size, self.action_size)
+        if arrays is None or len(arrays) == 5:  # forgotten, or a Dyna-Q model: the library rebuilds the canonical lists
+            self._set_state(self._lib.qe_population_set_model, arrays, 5)
+            return
+        before = self.planning_model
+        self._set_state(self._lib.qe_population_set_model, arrays[:5], 5)
+        try:
+            self._set_state(self._lib.qe_population_set_predecessors, arrays[5:], 2)
+        except Exception:  # the lists do not fit the model: a refused model changes nothing
+            self.planning_model = before
+            raise
+
+    @property
+    def sweep_queue(self) -> dict | None:
+        """``planning_order="prioritized"``: every run's priority queue, a dict of ``cells`` (int32 ``[runs,
+        queue_length]``: the cell ``s * A + a`` a slot holds, -1 for a free slot) and ``priorities`` (float64, 0.0 in a
+        free slot), in slot order.  Run state, carried like :attr:`eligibility_traces`.  Otherwise: None.  Setting None
+        empties every queue; a cell that is out of range, unseen in the model or held twice, a priority that is NaN or
+        negative, or a free slot with a priority other than 0 is a ``ValueError``."""
+        if self.planning_order != "prioritized":
+            return None
+        return self._state_dict_of(self._lib.qe_population_queue, _queue_specs(self.runs, self.queue_length))
+
+    @sweep_queue.setter
+    def sweep_queue(self, queue) -> None:
+        if self.planning_order != "prioritized":
+            if queue is not None:
+                msg = "a population without planning_order='prioritized' has no sweep queue"
+                raise ValueError(msg)
+            return
+        self._set_state(self._lib.qe_population_set_queue, queue_arrays(queue, self.runs, self.queue_length), 2)
 
     @property
     def counting(self) -> bool:
@@ -868,7 +990,8 @@ class QLearningPopulation:
         (SARSA: with its ``pending_actions``; after a reset, or without that key, every run picks at its first step;
         ``n_step > 1`` / ``tree_backup > 1``: with its ``n_step_window`` / ``tree_backup_window``; after a reset, or without
         that key, every window starts empty and the entries dropped are never updated; ``trace_decay``: with its ``eligibility_traces``; after a reset, or
-        without that key, every slot starts free).
+        without that key, every slot starts free; ``planning_order="prioritized"``: with its ``sweep_queue``; after a reset, or
+        without that key, every queue starts empty -- the model and its predecessor lists stay).
         ``log=False`` skips the per-episode returns (counts and means are always produced).  A run that meets a state
         without a selectable action raises ``IndexError`` naming the runs (``.runs``; ``.result`` holds the call's
         result, in which the other runs are unaffected)."""
@@ -914,7 +1037,8 @@ class QLearningPopulation:
 
     def restore_training_state(self, state_dict) -> None:
         """Continue exactly where ``state_dict`` (of ``run_steps``, e.g. un-pickled in a fresh process) left off: draw
-        counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``, ``tree_backup > 1``) window and (``trace_decay``) trace slots.  Tables: :meth:`load`; environments: pass
+        counter(s), every run's schedule values, (SARSA) pending action, (``n_step > 1``, ``tree_backup > 1``) window, (``trace_decay``) trace slots and (``planning_order="prioritized"``) queue.  Tables: :meth:`load`; the planning
+        model, which must be in place before the queue: :meth:`load_model`; environments: pass
         the dict to ``run_steps``."""
         for key, has in _CARRIED.items():
             if has(self):
@@ -1058,5 +1182,5 @@ class QLearningPopulation:
 
 
 __all__ = ["PolicyValues", "PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "model_arrays", "pending_array", "schedule_descriptor", "trace_arrays", "tree_window_arrays", "visit_count_array",
+           "model_arrays", "pending_array", "queue_arrays", "schedule_descriptor", "sweep_model_arrays", "trace_arrays", "tree_window_arrays", "visit_count_array",
            "window_arrays"]

@@ -102,7 +102,9 @@ typedef struct qe_rollout_stats {
                                 SARSA(lambda)), NV and masked as path 6, the slot count K in bits 24-29 and the trace
                                 kind (qe_trace_kind) in bit 30, which no other field of that path uses; path 13:
                                 population with Dyna-Q (qe_population_set_planning): NV and masked as path 6, and the
-                                planning updates per step in bits 24-30; path 14: population with visit counts
+                                planning updates per step in bits 24-30 -- with bit 4 set the planning order is
+                                prioritized sweeping (qe_population_set_sweeping) and bits 5-9 hold its queue length
+                                minus 1 --; path 14: population with visit counts
                                 (qe_population_set_visits): NV and masked as path 6, visit_lr in bit 4 and "some run's
                                 beta is above 0" in bit 5; path 15: population with n-step Tree Backup
                                 (qe_population_set_tree_backup): NV and masked as path 6, and n in bits 24-28 */
@@ -447,7 +449,49 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         planning is off, and from the upload for a next state outside [0, S) that is not -1, a count
  *                         that differs from the number of seen cells, or a list entry (below count) that is out of range,
  *                         unseen in the model or listed twice; entries from count on and the rewards and flags of unseen
- *                         cells are not read.
+ *                         cells are not read.  While sweeping is on (below) the upload also rebuilds every predecessor
+ *                         list in its canonical order and empties every queue.
+ *   qe_population_set_sweeping  prioritized sweeping (Moore & Atkeson 1993; Sutton & Barto 8.4) as the order of the planning
+ *                         updates: queue_length slots per run, 1 .. 32, and every run's threshold theta (finite, >= 0);
+ *                         queue_length 0 (thresholds ignored) turns it off, frees the index and the queues, and gives
+ *                         uniform Dyna-Q back.  It needs planning on.  Every run keeps, beside the model, a predecessor
+ *                         list per state x -- the seen cells whose model entry is (x, ., terminated = 0), most recently
+ *                         linked first -- and a queue of K (cell, priority) slots.  With inc(c, rho, m, tau) the increment
+ *                         the step's update of (Q[c], rho, m, tau) reports (of the table dtype; on a float32 table in vec
+ *                         mode the float64 increment before it is rounded), P(u) = |float64(u)| and rowmax(p) the maximum
+ *                         of row p over its valid columns as the table stands, a step with draw counter k is: Q-learning's
+ *                         step with increment u0; the model learns (s, a) -> (s', r, terminated) -- a linked cell whose next
+ *                         state changes or that turns terminated is unlinked by a walk from the head of its list, a cell
+ *                         that is not terminated and not linked goes to the head of the list of s', a cell whose next
+ *                         state and flag did not change keeps its place --; if P(u0) > theta, propagate(s); then at most n
+ *                         times: stop if the queue is empty, c = pop(), (p, rho, tau) = model[c], Q[c] = the update of
+ *                         (Q[c], rho, rowmax(p), tau) with the learning rate of step k and increment u, and if
+ *                         P(u) > theta, propagate(c / A).  propagate(x): m = rowmax(x); for every cell d of the list of x,
+ *                         head to tail, u = inc(d, model[d].reward, m, false) -- nothing is stored -- and if P(u) > theta,
+ *                         insert(d, P(u)).  insert(c, P): a live slot holding c keeps max(old, P); else the lowest free
+ *                         slot takes it; else the slot of the smallest priority (lowest index among equals) is replaced if
+ *                         P is strictly greater, and the newcomer is dropped if not.  pop(): the slot of the largest
+ *                         priority, lowest index among equals; it becomes free.  No draw is consumed and a NaN increment
+ *                         is never queued.  The index is knowledge like the model, the queue is run state like the trace
+ *                         slots.  Turning it on (or changing queue_length) builds the canonical index of the model in hand
+ *                         and empties the queues.  QE_ERR_INVALID: not a population engine, planning off, queue_length out
+ *                         of range, thresholds NULL, negative or not finite; QE_ERR_UNSUPPORTED: a (dtype, row stride)
+ *                         whose kernel is not built.
+ *   qe_population_sweeping  queue_length, 0 while sweeping is off (or a negative qe_status).
+ *   qe_population_predecessors / qe_population_set_predecessors  the index: head holds runs * S entries, the cell s * A + a
+ *                         at the head of each state's list or -1; next holds runs * S * A entries, the next cell of the
+ *                         same list, -1 at a tail and at a cell that is not linked.  The upload takes both, or both NULL:
+ *                         the canonical index of the model in hand -- its seen cells with terminated == 0 linked in
+ *                         visited-list order, each at the head of its next state's list.  An upload is checked against
+ *                         the model in hand, in O(S * A) per run: every node reached from head[x] is in range, seen, not
+ *                         terminated and has next state x, no node is reached twice, the nodes reached are all the seen
+ *                         cells that are not terminated, and every other cell holds -1; anything else is QE_ERR_INVALID and
+ *                         changes nothing.  Either upload empties every queue.
+ *   qe_population_queue / qe_population_set_queue  the queues: cells and priorities hold runs * K entries, run r's slot i at
+ *                         [r * K + i]; a free slot reads (-1, 0.0).  The upload takes both, or both NULL: every queue
+ *                         empty.  QE_ERR_INVALID from the upload for a cell that is out of range, unseen in the model or
+ *                         held by two slots of a run, a priority that is NaN or negative, or a free slot whose priority
+ *                         is not 0.  The four are QE_ERR_INVALID while sweeping is off.
  *   qe_population_set_visits  per-cell visit counts N(s, a) of every run, uint32, zero when counting is turned on, with a
  *                         count-based optimism bonus and, with visit_lr != 0, the sample-average learning rate.  `bonus`
  *                         holds every run's beta (NULL: all zero); NULL with visit_lr == 0 turns counting off and forgets
@@ -521,6 +565,12 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
                         int32_t* count);
 int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
                             const int32_t* visited, const int32_t* count);
+int qe_population_set_sweeping(qe_engine* e, int32_t queue_length, const double* thresholds /* [runs] */);
+int qe_population_sweeping(qe_engine* e);
+int qe_population_predecessors(qe_engine* e, int32_t* head, int32_t* next);
+int qe_population_set_predecessors(qe_engine* e, const int32_t* head, const int32_t* next);
+int qe_population_queue(qe_engine* e, int32_t* cells, double* priorities);
+int qe_population_set_queue(qe_engine* e, const int32_t* cells, const double* priorities);
 int qe_population_set_visits(qe_engine* e, const double* bonus /* [runs]; NULL: all zero */, int32_t visit_lr);
 int qe_population_visits(qe_engine* e, int32_t* on, int32_t* visit_lr, double* bonus);
 int qe_population_visit_counts(qe_engine* e, uint32_t* out);
