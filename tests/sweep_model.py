@@ -34,6 +34,21 @@ dropped if it is not.  ``pop()``: the slot of the largest priority, lowest index
 
 No draw is consumed; a NaN increment never passes ``P > theta``.  ``events`` counts what happened, for
 tests/test_sweep_cases.py; it has no part in the rule.  ``skip_planning`` (``DynaRuntime``'s hook) skips steps 3 and 4.
+
+The census beside the branches of the rule (``events``; none of it feeds back):
+
+* ``pop_tie``: a pop with at least two live slots at the largest priority; ``pop_inf``: the popped priority is infinite;
+* ``evict_tie``: an eviction with at least two slots at the smallest priority; ``dropped_equal``: a dropped newcomer whose
+  priority equals the smallest; ``insert_hole``: an insert into a free slot that lies below a live one;
+* ``unlink_head`` / ``unlink_tail``: the unlinked cell was the head / the last node of a list of two or more
+  (``unlink_inner``, as before: neither the head, in a list of three or more);
+* ``propagate_held`` / ``propagate_other``: ``propagate(x)`` with ``x`` the next observation, whose row the kernel holds
+  in registers, or another state;
+* ``threshold_equal_step`` / ``_plan`` / ``_propagate``: ``P == theta > 0`` at the comparison of step 3, of step 4 or of
+  ``propagate``; ``smallest_compared`` is the smallest non-zero priority (not NaN) any of the three sites has compared;
+* ``rowmax_hidden_nan`` / ``rowmax_valid_nan``: ``rowmax(p)`` of a row with a NaN in invalid columns only / in a valid one;
+* ``held_row_turns_nan``: a planning store puts the first NaN into the valid columns of the row of the next observation
+  (the kernel recomputes the NaN flag of the row it holds in registers).
 """
 
 from __future__ import annotations
@@ -60,6 +75,8 @@ class SweepRuntime(DynaRuntime):
         self.theta = float(theta)
         self.events = Counter()
         self.flag_flips = Counter()  # (cell, new flag) -> how often the cell's terminated flag changed to it
+        self.smallest_compared = np.inf
+        self.held = -1
         self._cols = {}
         super().__init__(algorithm, lr_schedule, exploration_rate_schedule, learn_mode, n=n, agent_id=agent_id, mask_of=mask_of)
 
@@ -92,15 +109,30 @@ class SweepRuntime(DynaRuntime):
     def _priority(u):
         return abs(float(np.float64(u)))
 
-    def _rowmax(self, p):
+    def _valid_cells_of(self, p):
         q = self.algorithm.q_table
         if self.mask_of is None:
-            row = q[p]
-        else:
-            if p not in self._cols:  # (the valid columns are a function of the observation alone: dyna_model.py)
-                self._cols[p] = self.mask_of(p)
-            row = q[p][self._cols[p]]
+            return q[p]
+        if p not in self._cols:  # (the valid columns are a function of the observation alone: dyna_model.py)
+            self._cols[p] = self.mask_of(p)
+        return q[p][self._cols[p]]
+
+    def _rowmax(self, p):
+        q = self.algorithm.q_table
+        row = self._valid_cells_of(p)
+        if np.isnan(row).any():
+            self.events["rowmax_valid_nan"] += 1
+        elif np.isnan(q[p]).any():
+            self.events["rowmax_hidden_nan"] += 1
         return np.max(row) if row.size else q.dtype.type(-np.inf)
+
+    def _passes(self, P, site):
+        """``P > theta`` of the named site, counted."""
+        if P == self.theta > 0:
+            self.events["threshold_equal_" + site] += 1
+        if 0 < P < self.smallest_compared:
+            self.smallest_compared = P
+        return P > self.theta
 
     def _update(self, s, a, reward, v, terminated, lr):
         self.last_priority = self._priority(self._increment(s, a, reward, v, terminated, lr))
@@ -120,12 +152,18 @@ class SweepRuntime(DynaRuntime):
         if -1 in self.cells:
             i = self.cells.index(-1)
             ev["insert_free"] += 1
+            if any(c2 >= 0 for c2 in self.cells[i + 1:]):
+                ev["insert_hole"] += 1
         else:
             i = int(np.argmin(self.priorities))  # (the first of the smallest)
             if not P > self.priorities[i]:
                 ev["dropped"] += 1
+                if P == self.priorities[i]:
+                    ev["dropped_equal"] += 1
                 return
             ev["evicted"] += 1
+            if self.priorities.count(self.priorities[i]) >= 2:
+                ev["evict_tie"] += 1
         self.cells[i], self.priorities[i] = c, P
 
     def pop(self):
@@ -133,6 +171,10 @@ class SweepRuntime(DynaRuntime):
         if not live:
             return -1
         i = max(live, key=lambda j: (self.priorities[j], -j))
+        if sum(self.priorities[j] == self.priorities[i] for j in live) >= 2:
+            self.events["pop_tie"] += 1
+        if np.isinf(self.priorities[i]):
+            self.events["pop_inf"] += 1
         c = self.cells[i]
         self.cells[i], self.priorities[i] = -1, 0.0
         return c
@@ -140,13 +182,14 @@ class SweepRuntime(DynaRuntime):
     def propagate(self, x, lr):
         A = self.algorithm.q_table.shape[1]
         m = self._rowmax(x)
+        self.events["propagate_held" if x == self.held else "propagate_other"] += 1
         inserted = 0
         for d in list(self.lists.get(x, ())):
             u = self._increment(d // A, d % A, self.model[d][1], m, False, lr)
             P = self._priority(u)
             if P != P:
                 self.events["nan_not_queued"] += 1
-            if P > self.theta:
+            if self._passes(P, "propagate"):
                 self.insert(d, P)
                 inserted += 1
             if d // A == x:
@@ -180,6 +223,10 @@ class SweepRuntime(DynaRuntime):
             lst = self.lists[old[0]]
             if len(lst) >= 3 and lst[0] != cell:
                 self.events["unlink_inner"] += 1
+            if lst[0] == cell:
+                self.events["unlink_head"] += 1
+            elif lst[-1] == cell:
+                self.events["unlink_tail"] += 1
             lst.remove(cell)
             self.events["unlinked"] += 1
         if not terminated and not stays:
@@ -189,10 +236,10 @@ class SweepRuntime(DynaRuntime):
             self.flag_flips[(cell, bool(terminated))] += 1
         if self.skip_planning:
             return next_states, infos
-        held = int((next_states["observation"] if isinstance(next_states, dict) else next_states)[0])
+        self.held = held = int((next_states["observation"] if isinstance(next_states, dict) else next_states)[0])
         with np.errstate(all="ignore"):
             # 3. the real step's own change reaches its predecessors
-            if P0 > self.theta:
+            if self._passes(P0, "step"):
                 self.propagate(s, lr)
             # 4. planning
             used = 0
@@ -204,10 +251,13 @@ class SweepRuntime(DynaRuntime):
                 used += 1
                 p, rho, tau = self.model[c]
                 m = self._rowmax(p)
+                clean = c // A == held and not np.isnan(self._valid_cells_of(held)).any()
                 self._update(c // A, c % A, rho, m, tau, lr)
                 if c // A == held:
                     self.events["patched_held_row"] += 1
-                if self.last_priority > self.theta:
+                    if clean and np.isnan(self._valid_cells_of(held)).any():
+                        self.events["held_row_turns_nan"] += 1
+                if self._passes(self.last_priority, "plan"):
                     self.propagate(c // A, lr)
             else:
                 self.events["all_pops_used"] += 1

@@ -1,12 +1,12 @@
 """GPU: the population's later update rules -- SARSA and Expected SARSA (k_rollout_runs_td), n-step (k_nstep_rollout),
 eligibility traces (k_trace_rollout), Dyna-Q (k_dyna_rollout), Double Q (k_double_rollout), n-step Tree Backup
-(k_tree_rollout) and the two greedy-evaluation kernels -- at the places the Q-learning kernel was already taken to
+(k_tree_rollout), prioritized sweeping (k_sweep_rollout) and the two greedy-evaluation kernels -- at the places the Q-learning kernel was already taken to
 (tests/test_gpu_population_limits.py): padded and degenerate row widths, the selection threshold at 10 / 11 actions on
 NaN tables, real columns that tie with the padding, draw counters and agent ids that wrap at 2^32, and carried state
 that goes through the host at a padded width.
 
 Every comparison is bit for bit against the NumPy model run of the same run (td_rules_model.py, n_step_model.py,
-trace_model.py, dyna_model.py, double_q_model.py, tree_backup_model.py), through the ``_check`` of the family's own test
+trace_model.py, dyna_model.py, double_q_model.py, tree_backup_model.py, sweep_model.py), through the ``_check`` of the family's own test
 module: tables, episode returns and their steps, counts, final observation / env word / running return, schedule
 values, draw counter and the family's carried state.  The single-table evaluation is compared with the standalone
 one-agent evaluation, as in test_gpu_population_eval.py.  No tolerance anywhere.  Every case asserts the build it
@@ -26,6 +26,7 @@ import pytest
 import test_gpu_double_q as dq
 import test_gpu_dyna as dy
 import test_gpu_n_step as ns
+import test_gpu_sweep as sw
 import test_gpu_td_rules as td
 import test_gpu_traces as tr
 import test_gpu_tree_backup as tb
@@ -34,6 +35,7 @@ from double_q_model import DoubleRun
 from dyna_model import DynaRun
 from n_step_model import NStepRun
 from oracle import envs as oenvs
+from sweep_model import SweepRun
 from table_mdp_model import TableMDPVecEnv, random_mdp
 from td_rules_model import TdRun
 from test_gpu_double_q import _run_flagged, special_tables
@@ -55,7 +57,9 @@ FAMILIES = (["sarsa", "expected_sarsa"] + [f"nstep-{rule}" for rule in ns.RULES]
             + [f"trace-{rule}-{kind}" for rule in tr.RULES for kind in tr.KINDS] + ["dyna", "double"])
 SIX = ["sarsa", "expected_sarsa", "nstep", "trace", "dyna", "double"]
 SEVEN = [*SIX, "tree"]  # appended: the six keep their indices, and with them their dtypes, learn modes and seeds
+EIGHT = [*SEVEN, "sweep"]  # appended likewise: prioritized sweeping, n = 4 updates per step from a queue of 4 slots
 TREE_FAMILIES = [f"tree-{n}" for n in tbc.HORIZONS]
+SWEEP_K = 4
 
 
 def _product():
@@ -63,7 +67,7 @@ def _product():
 
 
 def _rotated(family, i):
-    """The i-th member of one of the seven families: n-step and the traces rotate their rules and kinds, Tree Backup
+    """The i-th member of one of the eight families: n-step and the traces rotate their rules and kinds, Tree Backup
     its horizon."""
     if family == "nstep":
         return f"nstep-{ns.RULES[i % 2]}"
@@ -104,6 +108,9 @@ def family_kw(fam, M):
         return {"planning_steps": PLANNING}
     if kind == "tree":
         return {"tree_backup": int(rest[0])}
+    if kind == "sweep":  # (the thresholds cycle over 0, 1e-4 and 1e-2 by run, as in tests/test_gpu_sweep.py)
+        return {"planning_steps": PLANNING, "planning_order": "prioritized", "queue_length": SWEEP_K,
+                "sweep_threshold": sw._thetas(M)}
     return {"double_q": True}
 
 
@@ -124,6 +131,8 @@ def model_run(fam, env, r, sched, seed, dt, mode, q0=None, qb0=None):
         return DynaRun(env, gamma[r], eps_s[r], lr_s[r], n=PLANNING, q0=q0, **kw)
     if kind == "tree":  # (with the census of its branches and of the cut rows it reads: tests/tree_backup_cases.py)
         return tbc.with_census(TreeBackupRun(env, gamma[r], eps_s[r], lr_s[r], n=int(rest[0]), q0=q0, **kw))
+    if kind == "sweep":  # (its census is the model's own ``events``: tests/sweep_model.py)
+        return SweepRun(env, gamma[r], eps_s[r], lr_s[r], n=PLANNING, K=SWEEP_K, theta=sw.THETAS[r % 3], q0=q0, **kw)
     return DoubleRun(env, gamma[r], eps_s[r], lr_s[r], qa0=q0, qb0=qb0, **kw)
 
 
@@ -171,6 +180,8 @@ def reached(fam, pop, A, masked):
         dy._reached(pop, PLANNING, nv=nv, masked=masked)
     elif kind == "tree":
         tb._reached(pop, int(rest[0]), nv=nv, masked=masked)
+    elif kind == "sweep":
+        sw._reached(pop, PLANNING, SWEEP_K, nv=nv, masked=masked)
     else:
         dq._reached(pop, nv=nv, masked=masked)
 
@@ -178,7 +189,7 @@ def reached(fam, pop, A, masked):
 def snapshot(fam, pop):
     """What the comparison reads from the device after a call, downloaded once."""
     return {"a": pop.q_tables, "b": pop.q_tables_b if fam == "double" else None,
-            "model": pop.planning_model if fam == "dyna" else None}
+            "model": pop.planning_model if fam in ("dyna", "sweep") else None}
 
 
 def check(fam, pop, res, r, run, history, at, snap, counter):
@@ -193,6 +204,8 @@ def check(fam, pop, res, r, run, history, at, snap, counter):
         tr._check(pop, res, r, run, history, at, snap["a"], counter)
     elif kind == "dyna":
         dy._check(pop, res, r, run, history, at, snap["a"], counter, snap["model"])
+    elif kind == "sweep":  # (the queue is read from ``res.state_dict["sweep_queue"]``)
+        sw._check(pop, res, r, run, history, at, snap["a"], counter, snap["model"])
     else:
         dq._check(pop, res, r, run, history, at, snap["a"], snap["b"], counter)
 
@@ -222,7 +235,7 @@ def hash_case(fam, S, A, masked, dt, mode, runs, *, K=150, seed=0, env_seed=1, o
     return pop, res, done
 
 
-# ---- 1. padded and degenerate row widths, all seven training families -------------------------------------------------------
+# ---- 1. padded and degenerate row widths, all eight training families -------------------------------------------------------
 WIDTHS = [1, 2, 3, 5, 9, 17, 33, 63]
 WIDTH_CASES = [pytest.param(fam, A, masked, *COMBOS[(wi + 2 * int(masked) + fi) % 4],
                             id=f"{fam}-A{A}-{'masked' if masked else 'plain'}")
@@ -235,6 +248,13 @@ WIDTH_CASES += [pytest.param(fam, A, masked, *COMBOS[(wi + 2 * int(masked) + len
                 for wi, A in enumerate(WIDTHS) for masked in (False, True)
                 for fam in [TREE_FAMILIES[(wi + int(masked)) % 3]]]
 TREE_WIDTH_CASES = [p.values for p in WIDTH_CASES if group_of(p.values[0]) == "tree"]
+# prioritized sweeping, appended after it: S = 40 as well -- at S = 100 a planning store or a propagate meets the held
+# row too rarely
+SWEEP_S = 40
+WIDTH_CASES += [pytest.param("sweep", A, masked, *COMBOS[(wi + 2 * int(masked) + len(FAMILIES) + 1) % 4],
+                             id=f"sweep-A{A}-{'masked' if masked else 'plain'}")
+                for wi, A in enumerate(WIDTHS) for masked in (False, True)]
+SWEEP_WIDTH_CASES = [p.values for p in WIDTH_CASES if p.values[0] == "sweep"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -244,12 +264,47 @@ def tree_width_models(fam, A, masked, dt, mode):
     return hash_models(fam, TREE_S, A, masked, dt, mode, _sample(A))
 
 
+@functools.lru_cache(maxsize=None)
+def sweep_width_mdp(A, masked):
+    """The environment of a prioritized-sweeping width case: a random table MDP of three outcomes per cell.  On the hash
+    environment the next state of a cell never changes, so no cell is ever unlinked from a predecessor list."""
+    from dist_classicrl_amd.environments.device_envs import encode_table_mdp
+
+    arrays, isd, masks = random_mdp(SWEEP_S, A, 3, seed=70 + A, masked=masked)
+    return encode_table_mdp(*arrays, isd, masks)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_width_models(fam, A, masked, dt, mode):
+    """The same for a prioritized-sweeping width case."""
+    mdp = sweep_width_mdp(A, masked)
+    return run_models(fam, lambda r: TableMDPVecEnv(1, mdp, seed=3, agent_offset=r), _sample(A), 150, _schedules(M_ODD), 0,
+                      dt, mode)
+
+
+def table_case(fam, mdp, A, masked, dt, mode, models, *, K=150, seed=0, env_seed=3):
+    """``hash_case`` on a table environment, against the model runs ``models``."""
+    envs = _product()[1]
+    pop = population(fam, M_ODD, mdp.thr.shape[0], A, _schedules(M_ODD), seed, dt, mode)
+    res = pop.run_steps(K, envs.TabularMDPEnv(M_ODD, mdp, seed=env_seed))
+    reached(fam, pop, A, masked)
+    snap = snapshot(fam, pop)
+    done, flagged = models
+    assert not flagged and done
+    for r, (run, history, at) in done.items():
+        check(fam, pop, res, r, run, history, at, snap, K)
+    return pop, res, done
+
+
 @pytest.mark.parametrize(("fam", "A", "masked", "dt", "mode"), WIDTH_CASES)
 def test_every_padded_width_matches_the_model(fam, A, masked, dt, mode):
     tree = group_of(fam) == "tree"
-    S = 100 if fam == "dyna" else TREE_S if tree else 300
-    _, _, done = hash_case(fam, S, A, masked, dt, mode, _sample(A),
-                           models=tree_width_models(fam, A, masked, dt, mode) if tree else None)
+    if fam == "sweep":
+        _, _, done = table_case(fam, sweep_width_mdp(A, masked), A, masked, dt, mode, sweep_width_models(fam, A, masked, dt, mode))
+    else:
+        S = 100 if fam == "dyna" else TREE_S if tree else 300
+        _, _, done = hash_case(fam, S, A, masked, dt, mode, _sample(A),
+                               models=tree_width_models(fam, A, masked, dt, mode) if tree else None)
     if A > 1:  # (at A = 1 explore and greedy coincide and every row has one candidate: the walk is a fixed cycle)
         assert any(np.any(t) for run, _, _ in done.values() for t in tables_of(run)), "no compared run learned anything"
 
@@ -265,7 +320,7 @@ def _steps(fam):
 
 
 NAN_CASES = [pytest.param(family, A, masked, id=f"{family}-A{A}-{'masked' if masked else 'plain'}")
-             for family in SEVEN for A, masked in NAN_SHAPES]
+             for family in EIGHT for A, masked in NAN_SHAPES]
 
 
 @functools.lru_cache(maxsize=None)
@@ -273,7 +328,7 @@ def nan_case(family, A, masked):
     """The inputs and the model's side of one case: a dict of fam, dt, mode, sched, q0, qb0, done and flagged."""
     i = NAN_SHAPES.index((A, masked))
     fam = _rotated(family, i)
-    dt, mode = COMBOS[(i + SEVEN.index(family)) % 4]
+    dt, mode = COMBOS[(i + EIGHT.index(family)) % 4]
     sched = _schedules(M_ODD)
     q0, qb0 = dq.special_case("both", A, dt, S=NAN_S) if fam == "double" else (special_tables(M_ODD, NAN_S, A, dt, seed=A), None)
     done, flagged = run_models(fam, lambda r: hash_model_env(r, NAN_S, A, masked), range(M_ODD), _steps(fam), sched, 0, dt,
@@ -304,7 +359,7 @@ def test_the_selection_threshold_on_special_tables_matches_the_model(family, A, 
 
 
 # ---- 3. real columns that tie with the padding ---------------------------------------------------------------------------------
-TIE_FAMILIES = ["sarsa", "expected_sarsa", "dyna", "double", "tree-3"]
+TIE_FAMILIES = ["sarsa", "expected_sarsa", "dyna", "double", "tree-3", "sweep"]
 TIE_CASES = [pytest.param(fam, A, id=f"{fam}-A{A}") for fam in TIE_FAMILIES for A in (3, 5)]
 
 
@@ -351,6 +406,10 @@ def test_real_columns_that_tie_with_the_padding_keep_the_pick_inside_the_row(fam
         assert (pending < A).all() and (pending[list(c["done"])] >= 0).all()
     if group_of(fam) == "tree":  # ... and so does every action a completed run holds in its window
         assert (res.state_dict["tree_backup_window"]["actions"][list(c["done"])] < A).all()
+    if fam == "sweep":  # ... and every queue cell and every list link comes back in the host numbering s * A + a
+        cells, links = res.state_dict["sweep_queue"]["cells"], pop.planning_model["pred_next"]
+        assert (cells >= 0).any() and (links >= 0).any()
+        assert (cells < NAN_S * A).all() and (links < NAN_S * A).all() and (pop.planning_model["pred_head"] < NAN_S * A).all()
     # a pick at or above A would store into a padding column and leave the real cell as it was: the real columns of
     # every compared run equal the model's (above), and the runs differ from their start
     assert not np.array_equal(pop.q_tables, c["q0"], equal_nan=True)
@@ -360,24 +419,25 @@ def test_real_columns_that_tie_with_the_padding_keep_the_pick_inside_the_row(fam
 STEP0 = 2**32 - 70   # a 150-step call: the step whose successor counter is exactly 2^32 is step 69 of the call
 OFFSET = 2**32 - 30  # run r has agent id (OFFSET + r) mod 2^32: 2^32 - 30 .. 36
 WRAP_SHAPE = {"sarsa": (9, True), "expected_sarsa": (5, False), "nstep": (17, True), "trace": (3, False), "dyna": (5, True),
-              "double": (9, False), "tree": (33, True)}  # Tree Backup: a 64-bit lane mask
+              "double": (9, False), "tree": (33, True),  # Tree Backup: a 64-bit lane mask
+              "sweep": (33, False)}  # ... and sweeping the same unmasked: NV = 16, which no other sweep case reaches
 
 
-@pytest.mark.parametrize("family", SEVEN)
+@pytest.mark.parametrize("family", EIGHT)
 def test_a_step_counter_crossing_2_pow_32_matches_the_model(family):
-    i = SEVEN.index(family)
+    i = EIGHT.index(family)
     A, masked = WRAP_SHAPE[family]
     _, res, done = hash_case(_rotated(family, i), 200, A, masked, *COMBOS[i % 4], _sample(i), step0=STEP0)
     assert res.state_dict["rng_step"] == STEP0 + 150 > 2**32
 
 
-@pytest.mark.parametrize("family", SEVEN)
+@pytest.mark.parametrize("family", EIGHT)
 def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_model(family, tmp_path):
-    """Two calls of 75 steps; the second by a fresh population from the saved tables (Dyna-Q: and model) and the pickled
-    state dict.  The wrap is step 69 of the first call: the pending action, window, slots or model cross the boundary
-    five steps after it."""
+    """Two calls of 75 steps; the second by a fresh population from the saved tables (Dyna-Q and sweeping: and model)
+    and the pickled state dict.  The wrap is step 69 of the first call: the pending action, window, slots, model or
+    queue cross the boundary five steps after it."""
     envs = _product()[1]
-    i = SEVEN.index(family)
+    i = EIGHT.index(family)
     fam = _rotated(family, i + 1)
     A, masked = WRAP_SHAPE[family]
     dt, mode = COMBOS[(i + 1) % 4]
@@ -392,15 +452,19 @@ def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_m
     first = pop.run_steps(K, env())
     snap1 = snapshot(fam, pop)
     pop.save(tmp_path / "tables.npy")
-    if fam == "dyna":
+    if fam in ("dyna", "sweep"):
         pop.save_model(tmp_path / "model.npz")
     blob = pickle.dumps(first.state_dict)
     fresh = population(fam, M_ODD, S, A, sched, seed, dt, mode)
     sd = pickle.loads(blob)
     fresh.load(tmp_path / "tables.npy")
-    if fam == "dyna":
+    if fam in ("dyna", "sweep"):
         fresh.load_model(tmp_path / "model.npz")
     fresh.restore_training_state(sd)
+    if fam == "sweep":  # the 7-key model and the queue are the saved ones, and some compared queue carries an entry
+        dy._same_model(fresh.planning_model, snap1["model"])
+        dy._same_model(fresh.sweep_queue, first.state_dict["sweep_queue"])
+        assert (first.state_dict["sweep_queue"]["cells"][_sample(10 + i)] >= 0).any(), "every compared queue is empty at the cut"
     if family == "tree":  # the window carries entries from before the wrap through the pickle
         window = first.state_dict["tree_backup_window"]
         assert window["length"].max() == pop.tree_backup - 1, "the window must be non-empty at the cut"
@@ -419,7 +483,7 @@ def test_a_counter_wrap_next_to_a_saved_and_restored_call_boundary_matches_the_m
         check(fam, fresh, second, r, run, history, at, snap2, STEP0 + 2 * K)
 
 
-@pytest.mark.parametrize("family", ["trace", "dyna", "tree"])
+@pytest.mark.parametrize("family", ["trace", "dyna", "tree", "sweep"])
 def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(family):
     """The table environment hashes the step too (``step >> 32`` in its word), unlike the hash environment."""
     from dist_classicrl_amd.environments.device_envs import encode_table_mdp
@@ -428,7 +492,7 @@ def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(famil
     arrays, isd, masks = random_mdp(300, 9, 3, seed=6, masked=True)
     mdp = encode_table_mdp(*arrays, isd, masks)
     fam = _rotated(family, 0)  # (Tree Backup: n = 5)
-    dt, mode = COMBOS[{"trace": 1, "dyna": 2, "tree": 3}[family]]
+    dt, mode = COMBOS[{"trace": 1, "dyna": 2, "tree": 3, "sweep": 0}[family]]
     S, A, K, seed = 300, 9, 150, 2
     sched = _schedules(M_ODD)
     pop = population(fam, M_ODD, S, A, sched, seed, dt, mode)
@@ -444,10 +508,10 @@ def test_a_step_counter_crossing_2_pow_32_on_a_table_env_matches_the_model(famil
     assert res.episode_counts.sum() > 0
 
 
-@pytest.mark.parametrize("family", SEVEN)
+@pytest.mark.parametrize("family", EIGHT)
 def test_agent_ids_that_wrap_past_2_pow_32_match_the_model(family):
-    i = SEVEN.index(family)
-    A, masked = WRAP_SHAPE[family if family == "tree" else SIX[(i + 3) % 6]]  # (the six trade shapes among themselves)
+    i = EIGHT.index(family)
+    A, masked = WRAP_SHAPE[family if family in ("tree", "sweep") else SIX[(i + 3) % 6]]  # (the six trade shapes among themselves)
     runs = sorted(set(_sample(30 + i)) | {28, 29, 30, 31})  # ids 2^32 - 2, 2^32 - 1, 0 and 1
     hash_case(_rotated(family, i + 2), 200, A, masked, *COMBOS[(i + 2) % 4], runs, offset=OFFSET)
 

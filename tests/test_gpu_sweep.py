@@ -8,6 +8,7 @@ means to cover (path 13, bit 4, K, NV, masked and n).  ``_case`` names the cases
 model alone, that they reach every branch of the rule.
 """
 import copy
+import functools
 import pickle
 
 import numpy as np
@@ -55,10 +56,15 @@ def _case(name):
         return "bandit", {"episode_len": 7}, 1, 2, 140, 3, 4, 11, 1, False
     if name == "frozen":  # slippery: next states change and cells unlink
         return "table", {"mdp": _frozen_mdp(), "seed": 3}, 16, 4, 150, 5, 4, 11, 1, False
-    if name == "grid":
+    if name == "grid":  # at 150 steps this one learns nothing: the goal of the 6 x 6 grid is all but never reached, the
+        # tables of its first 12 runs stay zero and every step finds its queue empty -- it checks the walk and the model
         return "grid", {"side": 6, "seed": 2}, 36, 4, 150, 5, 4, 11, 1, False
-    if name == "tictactoe":
+    if name == "grid-small":  # 4 x 4: the goal is reached, its reward is swept back two moves and further
+        return "grid", {"side": 4, "seed": 2}, 16, 4, 150, 5, 4, 11, 1, False
+    if name == "tictactoe":  # (with five pops per step no call ends with anything queued)
         return "tictactoe", {"seed": 5}, 19683, 9, 60, 5, 4, 11, 4, True
+    if name == "tictactoe-n1":  # one pop per step: some runs end the call with entries in their queue
+        return "tictactoe", {"seed": 5}, 19683, 9, 60, 1, 4, 11, 4, True
     raise KeyError(name)
 
 
@@ -175,12 +181,18 @@ def test_on_the_bandit_every_cell_is_a_predecessor_of_the_one_state(dt, mode):
 
 # ---- 4. other environments ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize(("name", "dt", "mode"), [("frozen", np.float32, "iter"), ("frozen", np.float64, "vec"),
-                                                  ("grid", np.float32, "vec"), ("tictactoe", np.float64, "iter")])
+                                                  ("grid", np.float32, "vec"), ("tictactoe", np.float64, "iter"),
+                                                  ("grid-small", np.float32, "iter"), ("grid-small", np.float64, "iter"),
+                                                  ("grid-small", np.float64, "vec"), ("tictactoe-n1", np.float32, "vec")])
 def test_other_environments_match_the_model(name, dt, mode):
-    _, res, model, _ = _run_and_check(name, dt, mode)
+    _, res, model, runs = _run_and_check(name, dt, mode)
     assert res.episode_counts.sum() > 0
     if name == "frozen":
         assert (model["count"] < 150).all(), "no cell was observed twice: nothing was overwritten"
+    if name == "grid-small":  # (tests/test_sweep_cases.py: in most runs value reaches a state two moves from the goal)
+        assert 2 * sum(bool(run.q.any()) for run in runs.values()) >= M_ODD
+    if name == "tictactoe-n1":
+        assert (res.state_dict["sweep_queue"]["cells"] >= 0).any(), "every queue is empty at the end of the call"
 
 
 # ---- 5. NaN and infinities in the tables ---------------------------------------------------------------------------------------
@@ -505,7 +517,215 @@ def _walk(model, r, x):
     return out
 
 
-# ---- 10. the uniform order is untouched -----------------------------------------------------------------------------------------
+# ---- 10. a priority equal to the threshold: ``P > theta`` is strict at all three sites ---------------------------------------------
+THETA_EQUAL = [(np.float32, "iter"), (np.float64, "vec"), (np.float32, "vec")]  # (the last: the unrounded float64 increment)
+THETA_PROBE = 40
+
+
+@functools.lru_cache(maxsize=None)
+def equal_threshold_runs(dt, mode):
+    """``(thresholds, {run: (model run, history, steps)})`` of ``four-16-masked`` at 150 steps, where run r's threshold is
+    the smallest non-zero priority its model run at threshold 0 compares within 40 steps.  Every comparison before the
+    first with that priority is of 0 or of something greater, so it falls as at threshold 0, the history up to it is the
+    probe's, and the comparison ``P == theta`` takes place (tests/test_sweep_cases.py counts at which site)."""
+    name = "four-16-masked"
+    thetas = []
+    for run in model_runs(name, range(M_ODD), dt, mode, thetas=[0.0] * M_ODD).values():
+        run.run(THETA_PROBE)
+        thetas.append(run.rt.smallest_compared)
+    runs = model_runs(name, range(M_ODD), dt, mode, thetas=thetas)
+    return thetas, {r: (run, *run.run(_case(name)[4])) for r, run in runs.items()}
+
+
+@pytest.mark.parametrize(("dt", "mode"), THETA_EQUAL)
+def test_a_priority_equal_to_the_threshold_does_not_pass(dt, mode):
+    kind, p, S, A, steps, n, K, seed, nv, masked = _case("four-16-masked")
+    thetas, done = equal_threshold_runs(dt, mode)
+    assert all(0 < t < np.inf for t in thetas)
+    pop = _population(M_ODD, S, A, _schedules(M_ODD), seed, dt, mode, n, K, thetas)
+    res = pop.run_steps(steps, _device_env(kind, M_ODD, p))
+    _reached(pop, n, K, nv=nv, masked=masked)
+    tables, model = pop.q_tables, pop.planning_model
+    for r, (run, history, at) in done.items():
+        assert sum(run.rt.events[f"threshold_equal_{site}"] for site in ("step", "plan", "propagate")), r
+        _check(pop, res, r, run, history, at, tables, steps, model)
+
+
+# ---- 11. a call cut into launches: the queue goes LDS -> [slot][runs] -> LDS, and ``hi`` is rebuilt over holes ---------------------
+# 2^25 / runs / (1 + n) steps per launch, and at most 2^23 / runs in a logged call: from n = 3 on the first bound is the
+# smaller one and both calls are cut at the same steps, so n = 2.  40 000 runs: 209 steps per logged launch, 279 per
+# unlogged one
+CUT = {"M": 40_000, "K": 500, "S": 40, "A": 8, "n": 2, "queue": 4, "seed": 21}
+
+
+def _holes_below_a_live_slot(cells):
+    """Per run: some free slot lies below a live one."""
+    live = cells >= 0
+    above = np.flip(np.logical_or.accumulate(np.flip(live, axis=1), axis=1), axis=1)  # slot i or a later one is live
+    return (~live & above).any(axis=1)
+
+
+def _same_call_state(a, b):
+    a, b = dict(a), dict(b)
+    _same_model(a.pop("sweep_queue"), b.pop("sweep_queue"))
+    _same_state(a, b)
+
+
+def test_a_logged_call_cut_into_launches_equals_the_unlogged_call_the_halves_and_the_model():
+    from test_gpu_population_limits import _cycled_schedules
+
+    envs = _product()[1]
+    M, K, S, A, n, Q, seed = (CUT[k] for k in ("M", "K", "S", "A", "n", "queue", "seed"))
+    sched = _cycled_schedules(M)
+    thetas = _thetas(M)
+
+    def make():
+        return _population(M, S, A, sched, seed, np.float32, "iter", n, Q, thetas)
+
+    def env():
+        return envs.HashTabularEnv(M, S, A, seed=1, masked=True)
+
+    logged = make()
+    res = logged.run_steps(K, env())
+    _reached(logged, n, Q, nv=2, masked=True)
+    assert logged.last_stats["launches"] == 9  # 209 + 209 + 82 steps, each launch with its scan and its pack
+    tables, model = logged.q_tables, logged.planning_model
+    quiet = make()
+    res_q = quiet.run_steps(K, env(), log=False)
+    assert quiet.last_stats["launches"] == 2, "the unlogged call is cut differently: 279 + 221 steps"
+    assert np.array_equal(quiet.q_tables, tables)
+    assert np.array_equal(res_q.episode_counts, res.episode_counts)
+    assert np.array_equal(res_q.mean_returns, res.mean_returns, equal_nan=True)
+    _same_call_state(res_q.state_dict, res.state_dict)
+    _same_model(quiet.planning_model, model)
+    _same_model(quiet.sweep_queue, res.state_dict["sweep_queue"])
+    del quiet
+    halves = make()
+    e = env()
+    first = halves.run_steps(K // 2, e)
+    assert halves.last_stats["launches"] == 6  # 209 + 41 steps
+    at_cut = first.state_dict["sweep_queue"]["cells"]
+    assert _holes_below_a_live_slot(at_cut).any(), "no queue crosses the call boundary with a hole below a live slot"
+    second = halves.run_steps(K // 2, e, first.state_dict)
+    assert np.array_equal(halves.q_tables, tables)
+    assert np.array_equal(first.episode_counts + second.episode_counts, res.episode_counts)
+    at1, at2 = first.offsets, second.offsets
+    for r in range(M):  # the two calls' logs, joined run by run, are the one call's log
+        joined = np.concatenate([first.returns[at1[r]:at1[r + 1]], second.returns[at2[r]:at2[r + 1]]])
+        assert np.array_equal(joined, res.returns[res.offsets[r]:res.offsets[r + 1]]), r
+    _same_call_state(second.state_dict, res.state_dict)
+    _same_model(halves.planning_model, model)
+    _same_model(halves.sweep_queue, res.state_dict["sweep_queue"])
+    del halves
+    p = {"S": S, "A": A, "seed": 1, "masked": True}
+    eps_s, lr_s, gamma = sched
+    for r in (0, 1, 63, 64, 65, 1023, 1024, 1025, M // 2, M - 1):
+        run = SweepRun(_model_env("hash", r, p), gamma[r], eps_s[r], lr_s[r], n=n, K=Q, theta=thetas[r], seed=seed, dtype=np.float32,
+                       mode="iter", agent_id=r)
+        history, at = run.run(K)
+        _check(logged, res, r, run, history, at, tables, K, model)
+
+
+# ---- 12. a call that starts from an uploaded queue: a hole, a live zero and an infinity --------------------------------------------
+@pytest.mark.parametrize(("dt", "mode"), [(np.float32, "vec"), (np.float64, "iter")])
+def test_a_call_from_an_uploaded_queue_with_a_hole_a_zero_and_an_infinity_matches_the_model(dt, mode):
+    envs = _product()[1]
+    M, S, A, steps, n, K = M_ODD, 20, 5, 60, 3, 4  # rows of 8: the cell s * A + a lies at s * 8 + a on the device
+    sched = _schedules(M)
+    thetas = _thetas(M)
+    pop = _population(M, S, A, sched, 7, dt, mode, n, K, thetas)
+    e = envs.HashTabularEnv(M, S, A, seed=1, masked=True)
+    first = pop.run_steps(steps, e)
+    _reached(pop, n, K, nv=2, masked=True)
+    tables1, model1 = pop.q_tables, pop.planning_model
+    visited, count = model1["visited"], model1["count"]
+    assert (count >= 2).all()
+    queue = {"cells": np.full((M, K), -1, dtype=np.int32), "priorities": np.zeros((M, K))}
+    queue["cells"][:, 0], queue["cells"][:, 2] = visited[:, 0], visited[:, 1]
+    queue["priorities"][:, 2] = np.inf
+    assert (queue["cells"][:, [0, 2]] >= A).any(), "no uploaded cell has another offset on the device than on the host"
+    pop.sweep_queue = queue
+    _same_model(pop.sweep_queue, queue)
+    second = pop.run_steps(steps, e, {**first.state_dict, "sweep_queue": queue})
+    tables, model = pop.q_tables, pop.planning_model
+    p = {"S": S, "A": A, "seed": 1, "masked": True}
+    eps_s, lr_s, gamma = sched
+    popped_inf = 0
+    for r in range(M):
+        run = SweepRun(_model_env("hash", r, p), gamma[r], eps_s[r], lr_s[r], n=n, K=K, theta=thetas[r], seed=7, dtype=dt, mode=mode,
+                       agent_id=r)
+        history, at = run.run(steps)
+        assert np.array_equal(tables1[r], run.q), f"run {r}: table before the upload"
+        _check_sweep(model1, first.state_dict["sweep_queue"], r, run)
+        run.rt.cells = [int(c) for c in queue["cells"][r]]
+        run.rt.priorities = [float(x) for x in queue["priorities"][r]]
+        history, at = run.run(steps)
+        popped_inf += bool(run.rt.events["pop_inf"])
+        _check(pop, second, r, run, history, at, tables, 2 * steps, model)
+    assert popped_inf == M
+
+
+# ---- 12b. a planning store that puts the first NaN into the row held in registers ----------------------------------------------------
+NAN_UPLOAD = [(8, np.float32, "iter"), (16, np.float64, "vec")]  # list selection / NumPy-style selection
+NAN_UPLOAD_STEPS = (60, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def nan_upload_case(A, dt, mode):
+    """Four states, masked, n = 5, K = 4.  After 60 steps run r gets a NaN in column 0 (always valid) of row ``x = r % 4``
+    and a queue of up to four seen, linked cells of other rows whose model entry leads to ``x``, all at priority inf.
+    The next step pops them: each stores a NaN, and where its row is the next observation's the row the kernel holds
+    turns NaN under it (``held_row_turns_nan``).  Returns the tables and queues to upload and, per run, the model run
+    with the outcome of the 4 steps after the upload (None for a run the model flags)."""
+    name = f"four-{A}-masked"
+    _, _, S, _, _, n, K, _, _, _ = _case(name)
+    runs = model_runs(name, range(M_ODD), dt, mode)
+    tables = np.zeros((M_ODD, S, A), dtype=dt)
+    queue = {"cells": np.full((M_ODD, K), -1, dtype=np.int32), "priorities": np.zeros((M_ODD, K))}
+    out = {}
+    for r, run in runs.items():
+        before = run.run(NAN_UPLOAD_STEPS[0])
+        x = r % S
+        run.q[x, 0] = np.nan
+        tables[r] = run.q
+        into_x = [c for c, (nxt, _, term) in sorted(run.rt.model.items()) if nxt == x and not term and c // A != x][:K]
+        queue["cells"][r, :len(into_x)] = into_x
+        queue["priorities"][r, :len(into_x)] = np.inf
+        run.rt.cells, run.rt.priorities = [int(c) for c in queue["cells"][r]], [float(p) for p in queue["priorities"][r]]
+        try:
+            out[r] = (run, before, run.run(NAN_UPLOAD_STEPS[1]))
+        except IndexError:
+            out[r] = (run, before, None)
+    return tables, queue, out
+
+
+@pytest.mark.parametrize(("A", "dt", "mode"), NAN_UPLOAD)
+def test_a_planning_store_that_turns_the_held_row_nan_matches_the_model(A, dt, mode):
+    kind, p, S, _, _, n, K, seed, nv, masked = _case(f"four-{A}-masked")
+    tables0, queue, out = nan_upload_case(A, dt, mode)
+    k1, k2 = NAN_UPLOAD_STEPS
+    pop = _population(M_ODD, S, A, _schedules(M_ODD), seed, dt, mode, n, K, _thetas(M_ODD))
+    e = _device_env(kind, M_ODD, p)
+    first = pop.run_steps(k1, e)
+    pop.set_q_tables(tables0)
+    pop.sweep_queue = queue
+    try:
+        second, raised = pop.run_steps(k2, e, {**first.state_dict, "sweep_queue": queue}), []
+    except IndexError as err:
+        second, raised = err.result, err.runs
+    _reached(pop, n, K, nv=nv, masked=masked)
+    tables, model = pop.q_tables, pop.planning_model
+    assert raised == [r for r, (_, _, after) in out.items() if after is None]
+    turned = 0
+    for r, (run, (history, at), after) in out.items():
+        assert np.array_equal(first.run_returns(r), history) and np.array_equal(first.run_steps(r), at), r
+        if after is not None:
+            turned += bool(run.rt.events["held_row_turns_nan"])
+            _check(pop, second, r, run, *after, tables, k1 + k2, model)
+    assert turned >= 5, "too few compared runs turn the held row NaN"
+
+
+# ---- 13. the uniform order is untouched -----------------------------------------------------------------------------------------
 def test_the_uniform_order_is_the_default_and_keeps_its_five_keys():
     _, envs, _, QLearningPopulation = _product()
     got = []

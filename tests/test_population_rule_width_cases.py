@@ -20,6 +20,11 @@ Tree Backup (``tree_backup_model.py``) has conditions of its own, counted by ``t
   update reads one with a NaN in a valid column -- and some of either through the kernel's own walk of a row
   (``row_np_max_at``), which a horizon of 2 never takes.
 
+Prioritized sweeping (``sweep_model.py``) is counted by the model's own ``events``: the 16 width cases together reach the
+queue's, the lists' and the held row's branches, every one with more than one action inserts, uses all its pops and
+unlinks; the special-table cases take row maxima over hidden and over valid NaNs and pop infinite priorities; the wrap
+case crosses its call boundary with a queued entry.
+
 Every test prints the figures it asserts on (``pytest -s``).
 """
 import numpy as np
@@ -92,16 +97,20 @@ def test_every_family_meets_every_dtype_and_learn_mode_in_the_width_sweep():
     for p in cases.WIDTH_CASES:
         fam, _, _, dt, mode = p.values
         met.setdefault(cases.group_of(fam), set()).add((dt, mode))
-    assert sorted(met) == sorted([*cases.FAMILIES, "tree"])
+    assert sorted(met) == sorted([*cases.FAMILIES, "tree", "sweep"])
     assert all(len(v) == 4 for v in met.values()), met
     tree = cases.TREE_WIDTH_CASES
     assert [(A, masked) for _, A, masked, _, _ in tree] == [(A, masked) for A in cases.WIDTHS for masked in (False, True)]
     for fam, A, masked, _, _ in tree:
         assert fam == f"tree-{tbc.HORIZONS[(cases.WIDTHS.index(A) + int(masked)) % 3]}", (fam, A, masked)
-    # the ids, dtypes and learn modes of the other families' cases are those they had before Tree Backup was appended
+    # the ids, dtypes and learn modes of the other families' cases are those they had before Tree Backup and
+    # prioritized sweeping were appended
     assert [p.id for p in cases.WIDTH_CASES[:3]] == ["sarsa-A1-plain", "sarsa-A1-masked", "sarsa-A2-plain"]
     assert cases.WIDTH_CASES[len(cases.FAMILIES) * 16 - 1].id == "double-A63-masked"
-    assert len(cases.WIDTH_CASES) == (len(cases.FAMILIES) + 1) * 16
+    assert cases.WIDTH_CASES[(len(cases.FAMILIES) + 1) * 16 - 1].id == "tree-16-A63-masked"
+    assert len(cases.WIDTH_CASES) == (len(cases.FAMILIES) + 2) * 16
+    assert [(A, masked) for _, A, masked, _, _ in cases.SWEEP_WIDTH_CASES] == [(A, masked) for A in cases.WIDTHS for masked in (False, True)]
+    assert cases.SEVEN == [*cases.SIX, "tree"] and cases.EIGHT == [*cases.SEVEN, "sweep"]
 
 
 def _tree_totals(which, cases_of_horizon):
@@ -143,6 +152,65 @@ def test_the_tree_backup_width_cases_reach_every_source_of_the_value_at_the_cut(
     assert all(long.values()), long
     assert short["steady_cut_old"] == 0  # a window of one old entry has none after entry 0
     assert all(count for kind, count in short.items() if kind != "steady_cut_old"), short
+
+
+def _sweep_events(done):
+    """The sum of the model's event counters over the completed runs ``done``."""
+    total = {}
+    for run, _, _ in done.values():
+        for kind, count in run.rt.events.items():
+            total[kind] = total.get(kind, 0) + int(count)
+    return total
+
+
+def test_the_sweep_width_cases_reach_the_branches_of_the_queue_the_lists_and_the_held_row():
+    together = {}
+    for case in cases.SWEEP_WIDTH_CASES:
+        _, A, masked, dt, mode = case
+        done, flagged = cases.sweep_width_models(*case)
+        assert not flagged and sorted(done) == cases._sample(A)
+        got = _sweep_events(done)
+        print(f"sweep A={A} masked={masked} {np.dtype(dt).name} {mode}: {dict(sorted(got.items()))}")
+        for kind, count in got.items():
+            together[kind] = together.get(kind, 0) + count
+        if A > 1:
+            assert got.get("insert_free") and got.get("all_pops_used") and got.get("unlinked"), case
+    print(f"the 16 sweep width cases together: {dict(sorted(together.items()))}")
+    for kind in ("evicted", "dropped", "insert_raises", "insert_hole", "unlink_inner", "patched_held_row", "propagate_held",
+                 "propagate_other", "queue_ran_empty"):
+        assert together.get(kind), kind
+
+
+def test_the_sweep_threshold_cases_take_row_maxima_over_hidden_and_over_valid_nans():
+    total = {}
+    for A, masked in cases.NAN_SHAPES:
+        c = cases.nan_case("sweep", A, masked)
+        got = _sweep_events(c["done"])
+        print(f"sweep A={A} masked={masked}: " + ", ".join(f"{k} {got.get(k, 0)}" for k in
+                                                           ("rowmax_hidden_nan", "rowmax_valid_nan", "nan_not_queued", "pop_inf")))
+        if masked:
+            assert got.get("rowmax_hidden_nan"), (A, masked)  # the masked cases gather rows whose NaN is hidden
+        else:
+            assert not got.get("rowmax_hidden_nan")
+        for kind, count in got.items():
+            total[kind] = total.get(kind, 0) + count
+    for kind in ("rowmax_hidden_nan", "rowmax_valid_nan", "nan_not_queued", "pop_inf"):
+        assert total.get(kind), kind
+
+
+def test_the_sweep_wrap_case_crosses_its_call_boundary_with_a_queued_entry_in_a_compared_run():
+    i = cases.EIGHT.index("sweep")
+    A, masked = cases.WRAP_SHAPE["sweep"]
+    assert cases._nv(A) == 16 and not masked
+    dt, mode = cases.COMBOS[(i + 1) % 4]
+    queued = 0
+    for r in cases._sample(10 + i):
+        run = cases.model_run("sweep", cases.hash_model_env(r, 200, A, masked, 9), r, cases._schedules(cases.M_ODD), 4, dt, mode)
+        run.rt.step_counter = cases.STEP0
+        run.run(75)
+        queued += max(run.rt.cells) >= 0
+    print(f"sweep, two calls of 75 steps around 2^32: {queued} of {len(cases._sample(10 + i))} compared queues hold an entry at the cut")
+    assert queued >= 1
 
 
 def test_the_masked_tree_backup_threshold_cases_read_cut_rows_with_hidden_and_with_valid_nans():

@@ -141,12 +141,109 @@ def test_the_queue_by_hand():
     assert rt.cells == [7, 11, 10]
     assert rt.pop() == 7                     # the lowest index among equals
     assert rt.pop() == 10 and rt.pop() == 11 and rt.pop() == -1
-    assert rt.events == {"insert_free": 4, "insert_keeps": 1, "insert_raises": 1, "dropped": 1, "evicted": 1}
+    assert rt.events == {"insert_free": 4, "insert_keeps": 1, "insert_raises": 1, "dropped": 1, "evicted": 1,
+                         "dropped_equal": 1, "insert_hole": 1, "pop_tie": 1}  # (10 at 0.25; 11 below 10; 7 before 10)
     rt.insert(3, 2.0)
     rt.insert(4, 2.0)
     rt.insert(5, 2.0)
     rt.insert(6, 3.0)                        # the lowest index among the equal smallest
     assert rt.cells == [6, 4, 5]
+
+
+def _queue(cells, priorities):
+    rt = SweepRuntime.__new__(SweepRuntime)
+    rt.K, rt.events = len(cells), __import__("collections").Counter()
+    rt.cells, rt.priorities = list(cells), list(priorities)
+    return rt
+
+
+def test_the_census_of_the_tie_events_by_hand():
+    """Each queue is written out; the counter named beside it moves, and only where it should."""
+    # pop_tie: two live slots share the maximum -> the lower index; a hole and a smaller entry do not count
+    rt = _queue([5, -1, 6, 7], [2.0, 0.0, 2.0, 1.0])
+    assert rt.pop() == 5 and rt.events == {"pop_tie": 1}
+    assert rt.pop() == 6 and rt.pop() == 7 and rt.pop() == -1 and rt.events == {"pop_tie": 1}
+    # a free slot's 0.0 is not an entry: a single live zero is no tie
+    rt = _queue([-1, 9, -1], [0.0, 0.0, 0.0])
+    assert rt.pop() == 9 and not rt.events
+    # pop_inf
+    rt = _queue([3, 4], [1.0, np.inf])
+    assert rt.pop() == 4 and rt.events == {"pop_inf": 1}
+    rt = _queue([3, 4], [np.inf, np.inf])
+    assert rt.pop() == 3 and rt.events == {"pop_inf": 1, "pop_tie": 1}
+    # evict_tie: full, two slots at the smallest, the newcomer is greater -> the lower of them gives way
+    rt = _queue([1, 2, 3], [4.0, 0.5, 0.5])
+    rt.insert(8, 1.0)
+    assert rt.cells == [1, 8, 3] and rt.events == {"evicted": 1, "evict_tie": 1}
+    rt.insert(9, 2.0)                        # one smallest now: an eviction without a tie
+    assert rt.cells == [1, 8, 9] and rt.events == {"evicted": 2, "evict_tie": 1}
+    # dropped_equal: the newcomer equals the smallest; a smaller one is dropped without the count
+    rt.insert(10, 1.0)
+    assert rt.cells == [1, 8, 9] and rt.events == {"evicted": 2, "evict_tie": 1, "dropped": 1, "dropped_equal": 1}
+    rt.insert(10, 0.25)
+    assert rt.events["dropped"] == 2 and rt.events["dropped_equal"] == 1
+    # insert_equal: a live entry meets its own priority again
+    rt.insert(8, 1.0)
+    assert rt.priorities == [4.0, 1.0, 2.0] and rt.events["insert_equal"] == 1
+    # insert_hole: the lowest free slot lies below a live one; a free slot above every live one is no hole
+    rt = _queue([1, -1, 3, -1], [1.0, 0.0, 1.0, 0.0])
+    rt.insert(4, 0.5)
+    assert rt.cells == [1, 4, 3, -1] and rt.events == {"insert_free": 1, "insert_hole": 1}
+    rt.insert(5, 0.5)
+    assert rt.cells == [1, 4, 3, 5] and rt.events == {"insert_free": 2, "insert_hole": 1}
+
+
+def test_the_census_of_unlinks_thresholds_and_the_held_row_by_hand():
+    """A stochastic table MDP, whose cells change their outcome: the lists before and after each step say where the
+    unlinked cell stood, and the counters must say the same; the held state is the observation after the step."""
+    run = SweepRun(_env("table", 2), 0.93, *_schedules(), n=2, K=4, theta=0.0, seed=5, dtype=np.float64, agent_id=2)
+    rt = run.rt
+    A = run.q.shape[1]
+    run.run(1)
+    for _ in range(300):
+        before = {x: list(lst) for x, lst in rt.lists.items()}
+        ev0 = dict(rt.events)
+        s = run.obs
+        run.run(1)
+        cell = s * A + rt.last_action
+        moved = {k: rt.events[k] - ev0.get(k, 0) for k in ("unlinked", "unlink_head", "unlink_tail", "unlink_inner")}
+        was = [lst for lst in before.values() if cell in lst]
+        assert len(was) <= 1
+        if moved["unlinked"]:
+            lst = was[0]
+            assert moved["unlink_head"] == (lst[0] == cell)
+            assert moved["unlink_tail"] == (lst[-1] == cell and lst[0] != cell)
+            assert moved["unlink_inner"] == (len(lst) >= 3 and lst[0] != cell)
+        else:  # the cell was not linked, or it keeps its place in a list that no step 2 has touched
+            assert not any(moved.values())
+            assert not was or before[rt.model[cell][0]] == rt.lists[rt.model[cell][0]] == was[0]
+        assert rt.held == run.obs
+    ev = rt.events
+    assert ev["unlink_head"] and ev["unlink_tail"] and ev["unlinked"] >= ev["unlink_head"] + ev["unlink_tail"]
+    assert ev["propagate_held"] and ev["propagate_other"]
+    assert ev["propagate_held"] + ev["propagate_other"] == ev["propagate_some"] + ev["propagate_none"]
+    assert 0 < rt.smallest_compared < np.inf and not any(k.startswith("threshold_equal") for k in ev)
+    # ... and a threshold equal to a priority is counted at its site, and does not pass
+    rt.theta = 0.5
+    assert not rt._passes(0.5, "plan") and rt._passes(0.75, "plan") and not rt._passes(0.25, "step") and not rt._passes(np.nan, "step")
+    assert {k: v for k, v in ev.items() if k.startswith("threshold_equal")} == {"threshold_equal_plan": 1}
+    assert rt.smallest_compared <= 0.25
+    rt.theta = 0.0
+    assert not rt._passes(0.0, "propagate") and "threshold_equal_propagate" not in ev  # P == theta == 0 is not the event
+
+
+def test_the_census_of_rows_with_hidden_and_with_valid_nans_by_hand():
+    run = SweepRun(_env("hash_masked", 1), 0.93, *_schedules(), n=1, K=4, theta=0.0, seed=5, dtype=np.float32, agent_id=1)
+    rt, q = run.rt, run.q
+    q[:] = np.arange(q.size, dtype=np.float32).reshape(q.shape)
+    x = next(s for s in range(q.shape[0]) if len(rt.mask_of(s)) < q.shape[1])  # a state with a masked-out column
+    cols = rt.mask_of(x)
+    hidden, valid = int(np.setdiff1d(np.arange(q.shape[1]), cols)[0]), int(cols[0])
+    assert rt._rowmax(x) == q[x][cols].max() and not rt.events
+    q[x, hidden] = np.nan
+    assert rt._rowmax(x) == q[x][cols].max() and rt.events == {"rowmax_hidden_nan": 1}
+    q[x, valid] = np.nan
+    assert np.isnan(rt._rowmax(x)) and rt.events == {"rowmax_hidden_nan": 1, "rowmax_valid_nan": 1}
 
 
 # ---- 4. chaining ---------------------------------------------------------------------------------------------------------------------
