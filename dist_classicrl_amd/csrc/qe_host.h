@@ -26,8 +26,6 @@
 using namespace qe;
 
 namespace qe {
-struct NStepWin;  // the windows of the n-step rules (qe_rollout_nstep.h)
-struct TreeWin;   // the windows of n-step Tree Backup (qe_rollout_tree.h)
 template <typename T>
 struct TraceSlots;  // the slots of the eligibility traces (qe_rollout_trace.h)
 struct DynaModel;   // the learned model and visited list of Dyna-Q (qe_rollout_dyna.h)
@@ -199,9 +197,11 @@ struct PopState {
     // Double estimator (qe_population_set_double): table B, the engine's dtype, shape and row stride; the engine's own
     // table is A.  NULL: off (k_double_rollout / k_double_evaluate, qe_rollout_double.h).
     void* table_b = nullptr;
-    // n-step rules (qe_population_set_n_step): the horizon, 1 = the one-step kernels above.  n > 1: every run's
-    // window of at most n - 1 transitions between launches, [slot][runs], oldest first (k_nstep_rollout,
-    // qe_rollout_nstep.h); allocated when the horizon is set.
+    // The two multi-step methods: the horizon, 1 = the one-step kernels above.  n > 1: every run's window of at most
+    // n - 1 transitions between launches, [slot][runs], oldest first; allocated when the horizon is set.
+    //   win   the n-step rules (qe_population_set_n_step; k_nstep_rollout, qe_rollout_nstep.h);
+    //   tree  n-step Tree Backup (qe_population_set_tree_backup; k_tree_rollout, qe_rollout_tree.h): an action word
+    //         carries the entry's greedy flag in its top bit.
     struct Window {
         int n = 1;
         DevBuf<int32_t> len, s, a;
@@ -210,19 +210,8 @@ struct PopState {
             len.release(); s.release(); a.release(); r.release();
             n = 1;
         }
-    } win;
-    // n-step Tree Backup (qe_population_set_tree_backup): the horizon, 1 = the one-step kernel above.  n > 1: every run's
-    // window of at most n - 1 entries between launches, [slot][runs], oldest first; an action word carries the entry's
-    // greedy flag in its top bit (k_tree_rollout, qe_rollout_tree.h); allocated when the horizon is set.
-    struct TreeWindow {
-        int n = 1;
-        DevBuf<int32_t> len, s, a;
-        DevBuf<float> r;
-        void release() {
-            len.release(); s.release(); a.release(); r.release();
-            n = 1;
-        }
-    } tree;
+        RunWindows device() const { return RunWindows{n, len.p, s.p, a.p, r.p}; }
+    } win, tree;
     // Eligibility traces (qe_population_set_traces): k slots per run, 0 = off (the kernels above).  On: every run's
     // slots between launches, [slot][runs] (e holds k * runs values of the table dtype; a slot whose value is 0 is
     // free), and every run's lambda (k_trace_rollout, qe_rollout_trace.h); allocated when traces are set.
@@ -595,10 +584,10 @@ template <typename T, class Env>
 int64_t launch_runs_td(const RunsLaunch<T>& l, int rule, int32_t* pending);
 // ... with the n-step form of that rule and the runs' windows `w` (qe_inst_runs_nstep.hip)
 template <typename T, class Env>
-int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const NStepWin& w);
+int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const RunWindows& w);
 // ... with n-step Tree Backup, Q-learning's n-step form, and the runs' windows `w` (qe_inst_runs_tree.hip)
 template <typename T, class Env>
-int64_t launch_tree_runs(const RunsLaunch<T>& l, const TreeWin& w);
+int64_t launch_tree_runs(const RunsLaunch<T>& l, const RunWindows& w);
 // ... with eligibility traces: `rule` is QE_RULE_Q_LEARNING or QE_RULE_SARSA, `w` the runs' slots (qe_inst_runs_trace.hip)
 template <typename T, class Env>
 int64_t launch_trace_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const TraceSlots<T>& w);

@@ -15,8 +15,8 @@ static_assert(NSTEP_MAX < 32, "kernel_variant carries n in five bits");
 // One launch of l.steps steps of every run under `rule` with the windows `w`; the window of a workgroup is dynamic LDS.
 // Returns QE_VARIANT_RUNS_NSTEP | rule | NV | masked | n.
 template <typename T, class Env>
-int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const NStepWin& w) {
-    const size_t lds = nstep_lds_bytes(w.n);
+int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, const RunWindows& w) {
+    const size_t lds = window_lds_bytes(w.n);
     return launch_runs_build<Env>(l, QE_VARIANT_RUNS_NSTEP, [&](auto nv, auto mk, dim3 grid, dim3 block) -> int64_t {
         if (rule == QE_RULE_SARSA)
             hipLaunchKernelGGL((k_nstep_rollout<T, Env, decltype(nv)::value, decltype(mk)::value, TD_SARSA>), grid, block, lds, l.stream, l.c, l.ev, l.steps, pending, w);
@@ -27,4 +27,4 @@ int64_t launch_nstep_runs(const RunsLaunch<T>& l, int rule, int32_t* pending, co
     });
 }
 
-template int64_t launch_nstep_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, int, int32_t*, const NStepWin&);
+template int64_t launch_nstep_runs<QE_INST_T, QE_INST_ENV>(const RunsLaunch<QE_INST_T>&, int, int32_t*, const RunWindows&);

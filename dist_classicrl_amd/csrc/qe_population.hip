@@ -195,23 +195,21 @@ int pending_reserve(qe_engine* e) {
     return QE_OK;
 }
 
-// The n-step rules' windows, [slot][runs] with n - 1 slots: allocated for the horizon `n`, every window empty.
-int window_reserve(qe_engine* e, int n) {
-    PopState::Window& W = e->pop.win;
-    const size_t m = (size_t)e->pop.runs, cells = m * (size_t)(n - 1);
-    HIP_TRY(W.len.ensure(m)); HIP_TRY(W.s.ensure(cells)); HIP_TRY(W.a.ensure(cells)); HIP_TRY(W.r.ensure(cells));
-    HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return QE_OK;
-}
-
-// Tree Backup's windows, [slot][runs] with n - 1 slots: allocated for the horizon `n`, every window empty.
-int tree_reserve(qe_engine* e, int n) {
-    PopState::TreeWindow& W = e->pop.tree;
-    const size_t m = (size_t)e->pop.runs, cells = m * (size_t)(n - 1);
-    HIP_TRY(W.len.ensure(m)); HIP_TRY(W.s.ensure(cells)); HIP_TRY(W.a.ensure(cells)); HIP_TRY(W.r.ensure(cells));
-    HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+// The horizon of the windows `W` of a multi-step method := n, already checked.  The same horizon keeps the windows;
+// another one allocates them, [slot][runs] with n - 1 slots, every window empty; 1 gives them up.
+int window_resize(qe_engine* e, PopState::Window& W, int n) {
+    if (n == W.n) return QE_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (n > 1) {
+        const size_t m = (size_t)e->pop.runs, cells = m * (size_t)(n - 1);
+        HIP_TRY(W.len.ensure(m)); HIP_TRY(W.s.ensure(cells)); HIP_TRY(W.a.ensure(cells)); HIP_TRY(W.r.ensure(cells));
+        HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        W.release();
+    }
+    W.n = n;
     return QE_OK;
 }
 
@@ -362,6 +360,81 @@ void slots_to_device(const V* abi, U* dev, size_t m, size_t w, Keep keep) {
         for (size_t i = 0; i < w; ++i) dev[i * m + r] = keep(r, i) ? (U)abi[r * w + i] : U{};
 }
 
+// The windows `W` of a multi-step method at the ABI: [runs] lengths and [runs][n - 1] entries.  Tree Backup's action
+// words carry the greedy flag in their top bit; the n-step rules never set it, and `greedy` is NULL for them.
+int window_get(qe_engine* e, const PopState::Window& W, int32_t* len, int32_t* states, int32_t* actions, float* rewards,
+               uint8_t* greedy) {
+    const size_t m = (size_t)e->pop.runs, w = (size_t)(W.n - 1);
+    if (!w) return QE_OK;  // a one-step rule has no window: nothing to write
+    if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hs(m * w), ha(m * w), hf(m * w);
+    std::vector<float> hr(m * w);
+    HIP_TRY(hipMemcpyAsync(len, W.len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hs.data(), W.s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(ha.data(), W.a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(hr.data(), W.r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < m * w; ++k) {  // the action word: the action, and the flag in its top bit
+        hf[k] = ha[k] < 0 ? 1 : 0;
+        ha[k] &= ~TREE_GREEDY;
+    }
+    auto used = [&](size_t r, size_t i) { return (int32_t)i < len[r]; };  // slots past the length hold 0
+    slots_to_abi(hs.data(), states, m, w, used);
+    slots_to_abi(ha.data(), actions, m, w, used);
+    slots_to_abi(hr.data(), rewards, m, w, used);
+    slots_to_abi(hf.data(), greedy, m, w, used);
+    return QE_OK;
+}
+
+// The windows `W` := the caller's, checked before anything is written; a NULL `len` empties every window.  `method`
+// names the horizon's setting in a message; `flagged`: Tree Backup's windows, whose entries need `greedy` as well.
+int window_set(qe_engine* e, PopState::Window& W, const char* method, bool flagged, const int32_t* len, const int32_t* states,
+               const int32_t* actions, const float* rewards, const uint8_t* greedy) {
+    const size_t m = (size_t)e->pop.runs, w = (size_t)(W.n - 1);
+    if (!w) {
+        for (size_t r = 0; len && r < m; ++r)
+            if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with %s = 1", (long long)r, (int)len[r], method);
+        return QE_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    if (!len) {  // every window empty
+        HIP_TRY(hipMemsetAsync(W.len.p, 0, m * sizeof(int32_t), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return QE_OK;
+    }
+    if (!states || !actions || !rewards || (flagged && !greedy))
+        return qe_fail(QE_ERR_INVALID, "%s is NULL", flagged ? "states, actions, rewards or greedy" : "states, actions or rewards");
+    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
+        if (len[r] < 0 || len[r] > (int32_t)w)
+            return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
+        for (size_t i = 0; i < (size_t)len[r]; ++i) {
+            const int32_t s = states[r * w + i], a = actions[r * w + i];
+            if (s < 0 || s >= e->pop.S)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)e->pop.S);
+            if (a < 0 || a >= e->A)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
+            if (flagged && greedy[r * w + i] > 1)
+                return qe_fail(QE_ERR_INVALID, "window of run %lld: greedy flag %d is neither 0 nor 1", (long long)r, (int)greedy[r * w + i]);
+        }
+    }
+    std::vector<int32_t> hs(m * w), ha(m * w);
+    std::vector<float> hr(m * w);
+    auto used = [&](size_t r, size_t i) { return i < (size_t)len[r]; };
+    slots_to_device(states, hs.data(), m, w, used);
+    slots_to_device(actions, ha.data(), m, w, used);
+    slots_to_device(rewards, hr.data(), m, w, used);
+    for (size_t r = 0; flagged && r < m; ++r)  // the flag rides in the action word's top bit
+        for (size_t i = 0; i < (size_t)len[r]; ++i)
+            if (greedy[r * w + i]) ha[i * m + r] |= TREE_GREEDY;
+    HIP_TRY(hipMemcpyAsync(W.len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(W.s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(W.a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(W.r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 // The training launch of a population: the kernel of the first method that is on, in this order.
 template <typename T, class Env>
 int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
@@ -377,8 +450,8 @@ int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
     if (P.trace.k)
         return launch_trace_runs<T, Env>(l, P.rule, P.pending.p,
                                          TraceSlots<T>{P.trace.k, P.trace.kind, P.trace.s.p, P.trace.a.p, (T*)P.trace.e.p, P.trace.lambda.p});
-    if (P.tree.n > 1) return launch_tree_runs<T, Env>(l, TreeWin{P.tree.n, P.tree.len.p, P.tree.s.p, P.tree.a.p, P.tree.r.p});
-    if (P.win.n > 1) return launch_nstep_runs<T, Env>(l, P.rule, P.pending.p, NStepWin{P.win.n, P.win.len.p, P.win.s.p, P.win.a.p, P.win.r.p});
+    if (P.tree.n > 1) return launch_tree_runs<T, Env>(l, P.tree.device());
+    if (P.win.n > 1) return launch_nstep_runs<T, Env>(l, P.rule, P.pending.p, P.win.device());
     if (P.rule != QE_RULE_Q_LEARNING) return launch_runs_td<T, Env>(l, P.rule, P.pending.p);
     return launch_runs<T, Env>(l);
 }
@@ -821,16 +894,7 @@ int qe_population_set_n_step(qe_engine* e, int32_t n) {
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)", (int)n);
     if (n > 1 && P.trace.k)
         return qe_fail(QE_ERR_UNSUPPORTED, "n_step = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
-    if (n == P.win.n) return QE_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    if (n > 1) {
-        if (int rc = window_reserve(e, n)) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        P.win.release();
-    }
-    P.win.n = n;
-    return QE_OK;
+    return window_resize(e, P.win, n);
 }
 
 int qe_population_n_step(qe_engine* e) {
@@ -840,65 +904,13 @@ int qe_population_n_step(qe_engine* e) {
 
 int qe_population_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards) {
     if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.win.n - 1);
-    if (!w) return QE_OK;  // a one-step rule has no window: nothing to write
-    if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
-    HIP_TRY(hipSetDevice(e->device));
-    std::vector<int32_t> hs(m * w), ha(m * w);
-    std::vector<float> hr(m * w);
-    HIP_TRY(hipMemcpyAsync(len, P.win.len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hs.data(), P.win.s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(ha.data(), P.win.a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hr.data(), P.win.r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    auto used = [&](size_t r, size_t i) { return (int32_t)i < len[r]; };  // slots past the length hold 0
-    slots_to_abi(hs.data(), states, m, w, used);
-    slots_to_abi(ha.data(), actions, m, w, used);
-    slots_to_abi(hr.data(), rewards, m, w, used);
-    return QE_OK;
+    return window_get(e, e->pop.win, len, states, actions, rewards, nullptr);
 }
 
 int qe_population_set_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
                              const float* rewards) {
     if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.win.n - 1);
-    if (!w) {
-        for (size_t r = 0; len && r < m; ++r)
-            if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with n_step = 1", (long long)r, (int)len[r]);
-        return QE_OK;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    if (!len) {  // every window empty
-        HIP_TRY(hipMemsetAsync(P.win.len.p, 0, m * sizeof(int32_t), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return QE_OK;
-    }
-    if (!states || !actions || !rewards) return qe_fail(QE_ERR_INVALID, "states, actions or rewards is NULL");
-    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
-        if (len[r] < 0 || len[r] > (int32_t)w)
-            return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
-        for (size_t i = 0; i < (size_t)len[r]; ++i) {
-            const int32_t s = states[r * w + i], a = actions[r * w + i];
-            if (s < 0 || s >= P.S)
-                return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)P.S);
-            if (a < 0 || a >= e->A)
-                return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
-        }
-    }
-    std::vector<int32_t> hs(m * w), ha(m * w);
-    std::vector<float> hr(m * w);
-    auto used = [&](size_t r, size_t i) { return i < (size_t)len[r]; };
-    slots_to_device(states, hs.data(), m, w, used);
-    slots_to_device(actions, ha.data(), m, w, used);
-    slots_to_device(rewards, hr.data(), m, w, used);
-    HIP_TRY(hipMemcpyAsync(P.win.len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win.s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win.a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.win.r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return QE_OK;
+    return window_set(e, e->pop.win, "n_step", false, len, states, actions, rewards, nullptr);
 }
 
 int qe_population_set_tree_backup(qe_engine* e, int32_t n) {
@@ -919,16 +931,7 @@ int qe_population_set_tree_backup(qe_engine* e, int32_t n) {
         return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d: eligibility traces are on, and they are the multi-step method then (qe_population_set_traces)", (int)n);
     if (n > 1 && P.dyna.planning)
         return qe_fail(QE_ERR_UNSUPPORTED, "tree_backup = %d: planning is on, and Dyna-Q is a one-step method (qe_population_set_planning)", (int)n);
-    if (n == P.tree.n) return QE_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    if (n > 1) {
-        if (int rc = tree_reserve(e, n)) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        P.tree.release();
-    }
-    P.tree.n = n;
-    return QE_OK;
+    return window_resize(e, P.tree, n);
 }
 
 int qe_population_tree_backup(qe_engine* e) {
@@ -938,73 +941,13 @@ int qe_population_tree_backup(qe_engine* e) {
 
 int qe_population_tree_window(qe_engine* e, int32_t* len, int32_t* states, int32_t* actions, float* rewards, uint8_t* greedy) {
     if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.tree.n - 1);
-    if (!w) return QE_OK;  // the one-step rule has no window: nothing to write
-    if (!len) return qe_fail(QE_ERR_INVALID, "len is NULL");
-    HIP_TRY(hipSetDevice(e->device));
-    std::vector<int32_t> hs(m * w), ha(m * w), hf(m * w);
-    std::vector<float> hr(m * w);
-    HIP_TRY(hipMemcpyAsync(len, P.tree.len.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hs.data(), P.tree.s.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(ha.data(), P.tree.a.p, m * w * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpyAsync(hr.data(), P.tree.r.p, m * w * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (size_t k = 0; k < m * w; ++k) {  // the action word: the action, and the flag in its top bit
-        hf[k] = ha[k] < 0 ? 1 : 0;
-        ha[k] &= ~TREE_GREEDY;
-    }
-    auto used = [&](size_t r, size_t i) { return (int32_t)i < len[r]; };  // slots past the length hold 0
-    slots_to_abi(hs.data(), states, m, w, used);
-    slots_to_abi(ha.data(), actions, m, w, used);
-    slots_to_abi(hr.data(), rewards, m, w, used);
-    slots_to_abi(hf.data(), greedy, m, w, used);
-    return QE_OK;
+    return window_get(e, e->pop.tree, len, states, actions, rewards, greedy);
 }
 
 int qe_population_set_tree_window(qe_engine* e, const int32_t* len, const int32_t* states, const int32_t* actions,
                                   const float* rewards, const uint8_t* greedy) {
     if (int rc = need_population(e)) return rc;
-    PopState& P = e->pop;
-    const size_t m = (size_t)P.runs, w = (size_t)(P.tree.n - 1);
-    if (!w) {
-        for (size_t r = 0; len && r < m; ++r)
-            if (len[r] != 0) return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d with tree_backup = 1", (long long)r, (int)len[r]);
-        return QE_OK;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    if (!len) {  // every window empty
-        HIP_TRY(hipMemsetAsync(P.tree.len.p, 0, m * sizeof(int32_t), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return QE_OK;
-    }
-    if (!states || !actions || !rewards || !greedy) return qe_fail(QE_ERR_INVALID, "states, actions, rewards or greedy is NULL");
-    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes LDS with the length and the run's table with the entries)
-        if (len[r] < 0 || len[r] > (int32_t)w)
-            return qe_fail(QE_ERR_INVALID, "window of run %lld: length %d is outside [0, %d]", (long long)r, (int)len[r], (int)w);
-        for (size_t i = 0; i < (size_t)len[r]; ++i) {
-            const int32_t s = states[r * w + i], a = actions[r * w + i];
-            if (s < 0 || s >= P.S)
-                return qe_fail(QE_ERR_INVALID, "window of run %lld: state %d is outside [0, %lld)", (long long)r, (int)s, (long long)P.S);
-            if (a < 0 || a >= e->A)
-                return qe_fail(QE_ERR_INVALID, "window of run %lld: action %d is outside [0, %d)", (long long)r, (int)a, (int)e->A);
-            if (greedy[r * w + i] > 1)
-                return qe_fail(QE_ERR_INVALID, "window of run %lld: greedy flag %d is neither 0 nor 1", (long long)r, (int)greedy[r * w + i]);
-        }
-    }
-    std::vector<int32_t> hs(m * w), ha(m * w), packed(m * w);
-    std::vector<float> hr(m * w);
-    for (size_t k = 0; k < m * w; ++k) packed[k] = actions[k] | (greedy[k] ? TREE_GREEDY : 0);
-    auto used = [&](size_t r, size_t i) { return i < (size_t)len[r]; };
-    slots_to_device(states, hs.data(), m, w, used);
-    slots_to_device(packed.data(), ha.data(), m, w, used);
-    slots_to_device(rewards, hr.data(), m, w, used);
-    HIP_TRY(hipMemcpyAsync(P.tree.len.p, len, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.tree.s.p, hs.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.tree.a.p, ha.data(), m * w * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(P.tree.r.p, hr.data(), m * w * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return QE_OK;
+    return window_set(e, e->pop.tree, "tree_backup", true, len, states, actions, rewards, greedy);
 }
 
 int qe_population_set_traces(qe_engine* e, int32_t K, int32_t kind, const double* lambda) {

@@ -33,20 +33,9 @@ namespace qe {
 
 constexpr int NSTEP_MAX = 16;
 
-// The windows of all runs between launches (PopState, qe_host.h) and the horizon.
-struct NStepWin {
-    int32_t n;     // 2 .. NSTEP_MAX
-    int32_t* len;  // [M] entries of the run's window, <= n - 1
-    int32_t* s;    // [(n - 1) * M]: entry i of run r at [i * M + r], oldest first
-    int32_t* a;
-    float* r;
-};
-
-inline size_t nstep_lds_bytes(int n) { return (size_t)RUNS_BLOCK * (size_t)n * 12; }
-
 template <typename T, class Env, int NV, bool MASKED, int RULE>
 __global__ __launch_bounds__(RUNS_BLOCK) void k_nstep_rollout(RunsCtx<T> c, EnvCtx ev, long long steps, int32_t* pending,
-                                                             NStepWin w) {
+                                                             RunWindows w) {
     static_assert(RULE == TD_SARSA || RULE == TD_EXPECTED_SARSA, "an uncorrected n-step Q-learning is no off-policy method");
     using M = typename LaneMask<NV>::type;
     extern __shared__ int32_t nstep_lds[];

@@ -70,6 +70,19 @@ struct RunsCtx {
     const unsigned long long* step_off;  // [M] per-run offsets added to step0 (NULL: every run draws at step0 + t)
 };
 
+// The windows of all runs between launches (PopState, qe_host.h) and the horizon: what the two multi-step kernels,
+// k_nstep_rollout (qe_rollout_nstep.h) and k_tree_rollout (qe_rollout_tree.h), load at launch start and store at its end.
+struct RunWindows {
+    int32_t n;     // 2 .. NSTEP_MAX, TREE_MAX
+    int32_t* len;  // [M] entries of the run's window, <= n - 1
+    int32_t* s;    // [(n - 1) * M]: entry i of run r at [i * M + r], oldest first
+    int32_t* a;    // Tree Backup: the action | TREE_GREEDY if it was greedy
+    float* r;
+};
+
+// The dynamic LDS of a workgroup of either kernel: three planes [slot][lane] of n slots.
+inline size_t window_lds_bytes(int n) { return (size_t)RUNS_BLOCK * (size_t)n * 12; }
+
 // ---- what every population kernel shares ---------------------------------------------------------------------------
 // RunLane is the state one lane carries for its run through a launch, and the ONE copy of the protocol around a
 // kernel's own step.  k_rollout_runs and its siblings (qe_rollout_runs_td.h, _double.h, _nstep.h, _trace.h, _dyna.h,

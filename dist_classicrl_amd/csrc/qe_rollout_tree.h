@@ -37,18 +37,7 @@
 namespace qe {
 
 constexpr int TREE_MAX = 16;
-constexpr int32_t TREE_GREEDY = (int32_t)0x80000000u;  // the flag in an action word
-
-// The windows of all runs between launches (PopState, qe_host.h) and the horizon.
-struct TreeWin {
-    int32_t n;     // 2 .. TREE_MAX
-    int32_t* len;  // [M] entries of the run's window, <= n - 1
-    int32_t* s;    // [(n - 1) * M]: entry i of run r at [i * M + r], oldest first
-    int32_t* a;    // the action | TREE_GREEDY if it was greedy
-    float* r;
-};
-
-inline size_t tree_lds_bytes(int n) { return (size_t)RUNS_BLOCK * (size_t)n * 12; }
+constexpr int32_t TREE_GREEDY = (int32_t)0x80000000u;  // the flag in an action word (RunWindows::a)
 
 // np.max over the valid columns of row `row` of the run's table, 16 bytes (fp64: 2 x 16) at a time: the maximum and the
 // NaN flag are folded as the columns arrive, so the row never occupies registers of its own.  -inf if no column is valid.
@@ -90,7 +79,7 @@ __device__ __forceinline__ double row_np_max_at(const double* q, int64_t row, M 
 }
 
 template <typename T, class Env, int NV, bool MASKED>
-__global__ __launch_bounds__(RUNS_BLOCK) void k_tree_rollout(RunsCtx<T> c, EnvCtx ev, long long steps, TreeWin w) {
+__global__ __launch_bounds__(RUNS_BLOCK) void k_tree_rollout(RunsCtx<T> c, EnvCtx ev, long long steps, RunWindows w) {
     using M = typename LaneMask<NV>::type;
     extern __shared__ int32_t tree_lds[];
     const int64_t r = (int64_t)blockIdx.x * RUNS_BLOCK + threadIdx.x;

@@ -427,3 +427,22 @@ def test_refusals_and_arguments():
     # setting the horizon empties the windows
     assert lib.qe_population_set_n_step(pop.handle, 5) == 0 and lib.qe_population_n_step(pop.handle) == 5
     assert lib.qe_population_window(pop.handle, i32(length), None, None, None) == 0 and (length == 0).all()
+
+
+def test_the_window_calls_at_horizon_one():
+    """n_step = 1 has no window: the getter writes nothing, the setter takes only "every window empty"."""
+    import ctypes as C
+
+    _lib, _, _, QLearningPopulation = _product()
+    lib = _lib.load()
+    i32 = lambda a: _lib.ptr(a, C.c_int32)  # noqa: E731
+    pop = QLearningPopulation(8, 50, 4, update_rule="sarsa", n_step=1)
+    length = np.full(8, 7, dtype=np.int32)
+    assert lib.qe_population_window(pop.handle, i32(length), None, None, None) == 0 and (length == 7).all()
+    assert lib.qe_population_window(pop.handle, None, None, None, None) == 0
+    assert lib.qe_population_set_window(pop.handle, None, None, None, None) == 0
+    assert lib.qe_population_set_window(pop.handle, i32(np.zeros(8, dtype=np.int32)), None, None, None) == 0
+    one = np.array([0, 1, 0, 0, 0, 0, 0, 0], dtype=np.int32)
+    assert lib.qe_population_set_window(pop.handle, i32(one), None, None, None) == _lib.ERR_INVALID
+    assert "window of run 1: length 1 with n_step = 1" in lib.qe_last_error().decode()
+    assert lib.qe_population_n_step(pop.handle) == 1 and pop.n_step_window is None

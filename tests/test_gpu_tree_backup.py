@@ -456,3 +456,20 @@ def test_refusals_and_arguments():
     pop.run_steps(10, envs.HashTabularEnv(8, 50, 4))
     assert lib.qe_population_set_tree_backup(pop.handle, 5) == 0 and lib.qe_population_tree_backup(pop.handle) == 5
     assert lib.qe_population_tree_window(pop.handle, i32(out), None, None, None, None) == 0 and (out == 0).all()
+
+
+def test_the_window_calls_at_horizon_one():
+    """tree_backup = 1 has no window: the getter writes nothing, the setter takes only "every window empty"."""
+    _lib, _, _, QLearningPopulation = _product()
+    lib = _lib.load()
+    i32 = lambda a: _lib.ptr(a, C.c_int32)  # noqa: E731
+    pop = QLearningPopulation(8, 50, 4, tree_backup=1)
+    length = np.full(8, 7, dtype=np.int32)
+    assert lib.qe_population_tree_window(pop.handle, i32(length), None, None, None, None) == 0 and (length == 7).all()
+    assert lib.qe_population_tree_window(pop.handle, None, None, None, None, None) == 0
+    assert lib.qe_population_set_tree_window(pop.handle, None, None, None, None, None) == 0
+    assert lib.qe_population_set_tree_window(pop.handle, i32(np.zeros(8, dtype=np.int32)), None, None, None, None) == 0
+    one = np.array([0, 1, 0, 0, 0, 0, 0, 0], dtype=np.int32)
+    assert lib.qe_population_set_tree_window(pop.handle, i32(one), None, None, None, None) == _lib.ERR_INVALID
+    assert "window of run 1: length 1 with tree_backup = 1" in lib.qe_last_error().decode()
+    assert lib.qe_population_tree_backup(pop.handle) == 1 and pop.tree_backup_window is None
