@@ -40,6 +40,11 @@ TRACE_MAX = 32  # qe_population_set_traces
 PLANNING_MAX = 64  # qe_population_set_planning
 QUEUE_MAX = 32  # qe_population_set_sweeping
 PLANNING_ORDERS = ("uniform", "prioritized")
+MODEL_OUTCOMES_MAX = 8  # qe_population_set_model_outcomes
+# qe_population_set_model_outcomes: the (table dtype, 16-byte loads per fp32 row) builds of k_dyna_sample_rollout that are NOT
+# compiled because they do not fit the register file without scratch (dyna_sample_supported in csrc/qe_host.h, DESIGN
+# section 4.3c)
+DYNA_SAMPLE_REFUSED = frozenset()
 # qe_population_set_sweeping: the (table dtype, 16-byte loads per fp32 row) builds of k_sweep_rollout that are NOT compiled
 # because they do not fit the register file without scratch (sweep_supported in csrc/qe_host.h)
 SWEEP_REFUSED = frozenset()
@@ -65,7 +70,9 @@ def decode_variant(v: int) -> dict:
     path).  Path 13 (``population_dyna``, kernel ``k_dyna_rollout``) is the Q-learning population with Dyna-Q: NV and
     masked as path 6 and ``planning_steps`` in bits 24-30, a key that only this path's dict has; with bit 4 set the
     planning order is prioritized sweeping (kernel ``k_sweep_rollout``) and the dict gains ``prioritized`` (True) and
-    ``queue_length`` (bits 5-9 plus 1), two keys that no other dict has.  Path 14
+    ``queue_length`` (bits 5-9 plus 1), two keys that no other dict has; with bits 21-23 non-zero the model is the sample
+    model (kernel ``k_dyna_sample_rollout``) and the dict gains ``model_outcomes`` (those bits plus 1), a key that no
+    other dict has.  Path 14
     (``population_visit``, kernel ``k_visit_rollout``) is the Q-learning population with visit counts: NV and masked as path
     6, ``visit_lr`` in bit 4 and ``bonus`` (some run's beta is above 0) in bit 5, two keys that only this path's dict has.
     Path 15 (``population_tree``, kernel ``k_tree_rollout``) is the Q-learning population with n-step Tree Backup: NV and
@@ -93,6 +100,8 @@ def decode_variant(v: int) -> dict:
         if (v >> 4) & 1:
             out["prioritized"] = True
             out["queue_length"] = ((v >> 5) & 31) + 1
+        if (v >> 21) & 7:
+            out["model_outcomes"] = ((v >> 21) & 7) + 1
     if (v & 15) == 14:
         out["visit_lr"] = bool((v >> 4) & 1)
         out["bonus"] = bool((v >> 5) & 1)
@@ -111,6 +120,12 @@ def sweep_build_shipped(dtype, action_size: int) -> bool:
     """Whether ``k_sweep_rollout`` is built for rows of ``action_size`` actions of ``dtype`` (``SWEEP_REFUSED``)."""
     nv = max(4, 1 << (int(action_size) - 1).bit_length()) // 4
     return (np.dtype(dtype).name, nv) not in SWEEP_REFUSED
+
+
+def dyna_sample_build_shipped(dtype, action_size: int) -> bool:
+    """Whether ``k_dyna_sample_rollout`` is built for rows of ``action_size`` actions of ``dtype`` (``DYNA_SAMPLE_REFUSED``)."""
+    nv = max(4, 1 << (int(action_size) - 1).bit_length()) // 4
+    return (np.dtype(dtype).name, nv) not in DYNA_SAMPLE_REFUSED
 
 
 def variant_symbol(v: int, dtype: str = "float", env: str = "HashEnv", lanes_per_row: int = 4, vec: bool = False) -> str:
@@ -279,6 +294,10 @@ PROTOTYPES = {
     "qe_population_planning": (C.c_int, [_P]),
     "qe_population_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
     "qe_population_set_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _I32P, _I32P]),
+    "qe_population_set_model_outcomes": (C.c_int, [_P, C.c_int32]),
+    "qe_population_model_outcomes": (C.c_int, [_P]),
+    "qe_population_outcome_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _U32P, _I32P, _I32P]),
+    "qe_population_set_outcome_model": (C.c_int, [_P, _I32P, _F32P, _U8P, _U32P, _I32P, _I32P]),
     "qe_population_set_sweeping": (C.c_int, [_P, C.c_int32, _F64P]),
     "qe_population_sweeping": (C.c_int, [_P]),
     "qe_population_predecessors": (C.c_int, [_P, _I32P, _I32P]),

@@ -68,6 +68,17 @@ it is NOT in the state dict.  :attr:`planning_model` reads and sets it, ``save_m
 schedules), then passes the state dict to ``run_steps``.  ``double_q=True``, ``n_step > 1`` and ``trace_decay`` are
 refused with planning.  DESIGN section 4.3c defines the step; ``tests/dyna_model.py`` restates it on the oracle.
 
+``model_outcomes=K`` (2 .. 8, with ``planning_steps=n``; kernel ``k_dyna_sample_rollout``) gives Dyna-Q the sample model
+of Sutton & Barto ch. 8 for stochastic environments: every run remembers up to ``K`` distinct outcomes of every cell with
+their counts -- an outcome is told apart by its reward's 32 bits, its flag and, unless terminated, its next observation;
+when all slots are taken the rarest outcome is replaced -- and a planning update draws one of them in proportion to its
+count (a Philox stream of its own), so planning pulls ``Q[s, a]`` towards the expectation, not towards the last sample.
+All of it is integer work, so the runs equal a NumPy model bit for bit.  ``model_outcomes=1``, the default, is the
+last-outcome model above, unchanged.  :attr:`planning_model` gains the slot axis and ``outcome_counts``; a model saved by
+a last-outcome population loads as slot 0 with count 1.  Refused with ``planning_order="prioritized"`` (sweeping over a
+sample model needs expected updates, which are not built); everything Dyna-Q refuses is refused here too.  DESIGN
+section 4.3c defines the step; ``tests/dyna_sample_model.py`` restates it on the oracle.
+
 ``planning_order="prioritized"`` (with ``planning_steps=n``; kernel ``k_sweep_rollout``) replaces the uniform draws of
 Dyna-Q by prioritized sweeping (Moore & Atkeson 1993; Sutton & Barto 8.4): the ``n`` updates go where the table is about
 to change.  Every run keeps the predecessors of every state (the cells its model leads there from) and a queue of
@@ -213,7 +224,7 @@ def pending_array(values, runs) -> np.ndarray | None:
 # Dict-valued per-run state as the library takes it: one (key, shape, accepted dtype kinds, target dtype) per array, in
 # the order of the library's arguments.
 _CTYPES = {np.dtype(np.int32): C.c_int32, np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double,
-           np.dtype(np.uint8): C.c_uint8}
+           np.dtype(np.uint8): C.c_uint8, np.dtype(np.uint32): C.c_uint32}
 
 
 def _window_specs(runs, n_step):
@@ -236,6 +247,12 @@ def _model_specs(runs, state_size, action_size):
     cells = (runs, state_size, action_size)
     return (("next_states", cells, "iu", np.int32), ("rewards", cells, "f", np.float32), ("terminated", cells, "b", np.uint8),
             ("visited", (runs, state_size * action_size), "iu", np.int32), ("count", (runs,), "iu", np.int32))
+
+
+def _outcome_model_specs(runs, state_size, action_size, model_outcomes):
+    slots = (runs, state_size, action_size, model_outcomes)
+    return (("next_states", slots, "iu", np.int32), ("rewards", slots, "f", np.float32), ("terminated", slots, "b", np.uint8),
+            ("outcome_counts", slots, "iu", np.uint32), *_model_specs(runs, state_size, action_size)[3:])
 
 
 def _sweep_model_specs(runs, state_size, action_size):
@@ -320,6 +337,29 @@ def sweep_model_arrays(model, runs, state_size, action_size) -> tuple | None:
     return _spec_arrays("planning_model", model, _sweep_model_specs(runs, state_size, action_size), exact=True)
 
 
+def outcome_model_arrays(model, runs, state_size, action_size, model_outcomes) -> tuple | None:
+    """A ``planning_model`` of a population with ``model_outcomes=K > 1`` as the arrays the library takes: from the 6-key
+    dict, ``next_states`` (int32), ``rewards`` (float32), ``terminated`` (uint8) and ``outcome_counts`` (uint32: integers
+    in ``[0, 2^32)``), each ``[runs, S, A, K]``, then ``visited`` and ``count`` as in :func:`model_arrays`.  The 5-key dict
+    of a last-outcome population gives the five arrays of :func:`model_arrays` alone (the library then loads every
+    outcome as slot 0 with count 1); ``ValueError`` on anything else.  Whether slots, list and counts agree is the
+    library's check."""
+    if isinstance(model, dict) and len(model) == 5:
+        return model_arrays(model, runs, state_size, action_size)
+    specs = _outcome_model_specs(runs, state_size, action_size, model_outcomes)
+    if not isinstance(model, dict) or sorted(model) != sorted(key for key, *_ in specs):
+        return _spec_arrays("planning_model", model, specs, exact=True)  # (None, or the error that lists the keys)
+    # the counts fill uint32, which the exact check of the int32 arrays would refuse: they are checked on their own
+    (counts,) = _spec_arrays("planning_model", {"outcome_counts": model["outcome_counts"]}, specs[3:4])
+    given = np.asarray(model["outcome_counts"])
+    if given.size and (given.min() < 0 or given.max() >= 2 ** 32):
+        msg = f"planning_model['outcome_counts']: expected shape {specs[3][1]} of uint32, got values outside [0, 2^32)"
+        raise ValueError(msg)
+    rest = _spec_arrays("planning_model", {key: value for key, value in model.items() if key != "outcome_counts"},
+                        specs[:3] + specs[4:], exact=True)
+    return (*rest[:3], counts, *rest[3:])
+
+
 def queue_arrays(queue, runs, queue_length) -> tuple | None:
     """``sweep_queue`` of a state dict as the ``(cells, priorities)`` arrays the library takes (None: every queue empty):
     int32 ``[runs, queue_length]`` and float64 ``[runs, queue_length]``; ``ValueError`` on anything else."""
@@ -379,7 +419,9 @@ class QLearningPopulation:
     the updates replay cells drawn uniformly from the seen ones) or "prioritized" (prioritized sweeping: the updates go to
     the cells whose value is about to change, taken from a queue of ``queue_length`` slots per run, 1 .. 32, that the
     predecessors of every changed state enter when their increment would exceed ``sweep_threshold`` -- one finite number
-    >= 0 or a sequence of ``runs``; :attr:`sweep_queue`); it needs ``planning_steps >= 1``.  ``exploration_bonus`` (None: none; else one
+    >= 0 or a sequence of ``runs``; :attr:`sweep_queue`); it needs ``planning_steps >= 1``.  ``model_outcomes`` (1 .. 8, default 1: the
+    last-outcome model) is the number of distinct outcomes the planning model keeps per cell; above 1 it needs
+    ``planning_steps >= 1`` and the uniform order.  ``exploration_bonus`` (None: none; else one
     finite beta >= 0 or a sequence of ``runs``) adds ``beta / sqrt(N(s, a))`` to the row the pick sees and ``visit_lr=True``
     divides the learning rate by ``N(s, a)``; either turns on the visit counts (:attr:`visit_counts`), for "q_learning"
     without ``double_q``, ``n_step``, ``trace_decay`` or ``planning_steps``.  Schedules are ``ConstantSchedule``, ``LinearSchedule`` or ``ExponentialSchedule``; after each
@@ -389,7 +431,7 @@ class QLearningPopulation:
                  exploration_rate_schedule=None, seed=0, dtype=np.float64, learn_mode="iter", device=0,
                  update_rule="q_learning", double_q=False, n_step=1, trace_decay=None, trace_length=16,
                  trace_kind="replacing", planning_steps=0, exploration_bonus=None, visit_lr=False, tree_backup=1,
-                 planning_order="uniform", sweep_threshold=0.0, queue_length=16):
+                 planning_order="uniform", sweep_threshold=0.0, queue_length=16, model_outcomes=1):
         self.runs = int(runs)
         self.state_size = int(state_size)
         self.action_size = int(action_size)
@@ -485,6 +527,20 @@ class QLearningPopulation:
             self.sweep_threshold = theta
             self.queue_length = int(queue_length)
         self.planning_order = planning_order
+        _check_int("model_outcomes", model_outcomes, 1, _lib.MODEL_OUTCOMES_MAX)
+        if model_outcomes > 1:
+            if planning_steps < 1:
+                msg = f"model_outcomes={model_outcomes} sizes the planning model: it needs planning_steps >= 1"
+                raise ValueError(msg)
+            if planning_order == "prioritized":
+                msg = (f"model_outcomes={model_outcomes} with planning_order='prioritized': sweeping over a sample model needs "
+                       "expected updates, which are not built")
+                raise ValueError(msg)
+            if not _lib.dyna_sample_build_shipped(self.dtype, self.action_size):
+                msg = (f"model_outcomes={model_outcomes}: the kernel for {self.dtype} rows of {self.action_size} actions is not "
+                       "built (it does not fit the register file)")
+                raise ValueError(msg)
+        self.model_outcomes = int(model_outcomes)
         if not isinstance(visit_lr, (bool, np.bool_)):
             msg = f"visit_lr must be a bool, got {visit_lr!r}"
             raise ValueError(msg)
@@ -594,6 +650,8 @@ class QLearningPopulation:
                                                           _lib.ptr(self.trace_decay, C.c_double)))
         if self.planning_steps:
             _lib.check(self._lib.qe_population_set_planning(self._h, self.planning_steps))
+        if self.model_outcomes > 1:
+            _lib.check(self._lib.qe_population_set_model_outcomes(self._h, self.model_outcomes))
         if self.planning_order == "prioritized":
             _lib.check(self._lib.qe_population_set_sweeping(self._h, self.queue_length, _lib.ptr(self.sweep_threshold, C.c_double)))
         if self.counting:
@@ -738,9 +796,22 @@ class QLearningPopulation:
         another next state or reached twice, a seen cell left out, an unlinked cell not at -1) are a ``ValueError`` and
         change nothing -- or the 5-key dict of a Dyna-Q population, whose lists are rebuilt in the canonical order: the seen
         cells that are not terminated linked in visited-list order, each at the head of its next state's list.  Setting
-        or forgetting the model empties every run's :attr:`sweep_queue`."""
+        or forgetting the model empties every run's :attr:`sweep_queue`.
+
+        ``model_outcomes=K > 1`` keeps up to ``K`` outcomes per cell: ``next_states``, ``rewards`` and ``terminated`` have
+        the shape ``[runs, S, A, K]`` and ``outcome_counts`` (uint32, the same shape) says how often each was observed; the
+        occupied slots of a cell come first, in order of first observation, and a free slot reads -1, 0.0, False, 0.
+        The setter takes that 6-key dict -- an occupied slot behind a free one or with count 0, a free slot with a count,
+        two slots of a cell holding the same outcome, or counts of a cell adding up to more than ``2^32 - 1`` are a
+        ``ValueError`` and change nothing -- or the 5-key dict of a last-outcome population, whose outcomes load as
+        slot 0 with count 1."""
         if not self.planning_steps:
             return None
+        if self.model_outcomes > 1:
+            specs = _outcome_model_specs(self.runs, self.state_size, self.action_size, self.model_outcomes)
+            model = self._state_dict_of(self._lib.qe_population_outcome_model, specs)
+            model["terminated"] = model["terminated"].astype(bool)
+            return model
         model = self._state_dict_of(self._lib.qe_population_model, _model_specs(self.runs, self.state_size, self.action_size))
         model["terminated"] = model["terminated"].astype(bool)
         if self.planning_order == "prioritized":
@@ -754,6 +825,13 @@ class QLearningPopulation:
             if model is not None:
                 msg = "a population without planning_steps has no planning model"
                 raise ValueError(msg)
+            return
+        if self.model_outcomes > 1:
+            arrays = outcome_model_arrays(model, self.runs, self.state_size, self.action_size, self.model_outcomes)
+            if arrays is not None and len(arrays) == 5:  # a last-outcome model: the library loads it as slot 0, count 1
+                self._set_state(self._lib.qe_population_set_model, arrays, 5)
+            else:
+                self._set_state(self._lib.qe_population_set_outcome_model, arrays, 6)
             return
         if self.planning_order != "prioritized":
             self._set_state(self._lib.qe_population_set_model, model_arrays(model, self.runs, self.state_size, self.action_size), 5)
@@ -1182,5 +1260,5 @@ class QLearningPopulation:
 
 
 __all__ = ["PolicyValues", "PopulationEval", "PopulationRun", "PopulationTraining", "QLearningPopulation", "advance_descriptor",
-           "model_arrays", "pending_array", "queue_arrays", "schedule_descriptor", "sweep_model_arrays", "trace_arrays", "tree_window_arrays", "visit_count_array",
+           "model_arrays", "outcome_model_arrays", "pending_array", "queue_arrays", "schedule_descriptor", "sweep_model_arrays", "trace_arrays", "tree_window_arrays", "visit_count_array",
            "window_arrays"]

@@ -15,6 +15,7 @@ namespace qe {
 constexpr uint32_t STREAM_POLICY = 0;
 constexpr uint32_t STREAM_ENV = 1;
 constexpr uint32_t STREAM_PLAN = 2;  // Dyna-Q's planning draws: block b of a step at STREAM_PLAN | b << 8 (qe_rollout_dyna.h)
+constexpr uint32_t STREAM_OUTCOME = 3;  // the sample model's outcome draws, blocked like STREAM_PLAN (qe_rollout_dyna_sample.h)
 
 struct U4 {
     uint32_t x, y, z, w;

@@ -4,6 +4,7 @@
 // them into launches, compacts the per-run episode-log segments and reports.  The per-run draw counters live here too.
 #include "qe_host.h"
 #include "qe_rollout_dyna.h"
+#include "qe_rollout_dyna_sample.h"
 #include "qe_rollout_nstep.h"
 #include "qe_rollout_sweep.h"
 #include "qe_rollout_trace.h"
@@ -251,7 +252,13 @@ int traces_clear(qe_engine* e) {
 int model_clear(qe_engine* e) {
     PopState& P = e->pop;
     const size_t m = (size_t)P.runs;
-    HIP_TRY(hipMemsetAsync(P.dyna.entry.p, 0xFF, m * (size_t)P.S * (size_t)e->ld * sizeof(uint2), e->stream));  // DYNA_UNSEEN
+    const size_t cells = m * (size_t)P.S * (size_t)e->ld;
+    if (P.dyna.outcomes > 1) {  // the sample model: every slot free (count 0; a free slot's key reads next_obs 0, reward 0.0f)
+        HIP_TRY(hipMemsetAsync(P.dyna.ocnt.p, 0, cells * (size_t)P.dyna.outcomes * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(P.dyna.okey.p, 0, cells * (size_t)P.dyna.outcomes * sizeof(uint2), e->stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(P.dyna.entry.p, 0xFF, cells * sizeof(uint2), e->stream));  // DYNA_UNSEEN
+    }
     HIP_TRY(hipMemsetAsync(P.dyna.count.p, 0, m * sizeof(int32_t), e->stream));
     if (P.sweep.k) {  // prioritized sweeping: every list and every queue empty with it
         HIP_TRY(hipMemsetAsync(P.sweep.head.p, 0xFF, m * (size_t)P.S * sizeof(int32_t), e->stream));
@@ -445,6 +452,9 @@ int64_t launch_training(const qe_engine* e, const RunsLaunch<T>& l) {
     if (P.dyna.planning && P.sweep.k)
         return launch_sweep_runs<T, Env>(l, DynaModel{P.dyna.planning, P.dyna.entry.p, P.dyna.visited.p, P.dyna.count.p, P.S * (int64_t)e->A},
                                          SweepState{P.sweep.k, P.sweep.head.p, P.sweep.next.p, P.sweep.cell.p, P.sweep.pri.p, P.sweep.theta.p});
+    if (P.dyna.planning && P.dyna.outcomes > 1)
+        return launch_dyna_sample_runs<T, Env>(l, SampleModel{P.dyna.planning, P.dyna.outcomes, P.dyna.ocnt.p, P.dyna.okey.p, P.dyna.visited.p,
+                                                              P.dyna.count.p, P.S * (int64_t)e->A});
     if (P.dyna.planning)
         return launch_dyna_runs<T, Env>(l, DynaModel{P.dyna.planning, P.dyna.entry.p, P.dyna.visited.p, P.dyna.count.p, P.S * (int64_t)e->A});
     if (P.trace.k)
@@ -1123,6 +1133,8 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
     if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    if (P.dyna.outcomes > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED, "the model keeps %d outcomes per cell: read it with qe_population_outcome_model", P.dyna.outcomes);
     const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
     HIP_TRY(hipSetDevice(e->device));
     std::vector<int32_t> hc(m);
@@ -1170,6 +1182,21 @@ int qe_population_set_model(qe_engine* e, const int32_t* next_states, const floa
     if (!next_states || !rewards || !terminated || !visited || !count)
         return qe_fail(QE_ERR_INVALID, "next_states, rewards, terminated, visited or count is NULL");
     const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld;
+    if (P.dyna.outcomes > 1) {  // a last-outcome model loads into the sample model as slot 0, observed once
+        const size_t K = (size_t)P.dyna.outcomes, cells = m * S * A;
+        std::vector<int32_t> nx(cells * K, -1);
+        std::vector<float> rw(cells * K, 0.0f);
+        std::vector<uint8_t> tm(cells * K, 0);
+        std::vector<uint32_t> cn(cells * K, 0u);
+        for (size_t c = 0; c < cells; ++c) {
+            if (next_states[c] == -1) continue;
+            nx[c * K] = next_states[c];
+            rw[c * K] = rewards[c];
+            tm[c * K] = terminated[c] ? 1 : 0;
+            cn[c * K] = 1u;
+        }
+        return qe_population_set_outcome_model(e, nx.data(), rw.data(), tm.data(), cn.data(), visited, count);
+    }
     std::vector<uint2> he(m * S * ld, make_uint2(DYNA_UNSEEN, DYNA_UNSEEN));
     std::vector<int32_t> hv(m * S * A, 0);
     std::vector<uint8_t> listed(S * A);
@@ -1213,6 +1240,194 @@ int qe_population_set_model(qe_engine* e, const int32_t* next_states, const floa
     return QE_OK;
 }
 
+int qe_population_set_model_outcomes(qe_engine* e, int32_t outcomes) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (outcomes < 1 || outcomes > DYNA_OUTCOMES_MAX)
+        return qe_fail(QE_ERR_INVALID, "model_outcomes must be in 1 .. %d, got %d", DYNA_OUTCOMES_MAX, (int)outcomes);
+    if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "model_outcomes sizes the planning model: planning is off (qe_population_set_planning)");
+    if (outcomes == P.dyna.outcomes) return QE_OK;  // the model is knowledge and stays
+    if (outcomes > 1 && P.sweep.k)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "model_outcomes = %d: prioritized sweeping is on, and sweeping over a sample model needs expected updates, which "
+                       "are not built (qe_population_set_sweeping)",
+                       (int)outcomes);
+    if (outcomes > 1 && (e->ld > 64 || !dyna_sample_supported(e->dtype == QE_F32, e->ld / 4)))
+        return qe_fail(QE_ERR_UNSUPPORTED, "model_outcomes = %d: the kernel for %s rows of %d actions is not built (it does not fit the register file)",
+                       (int)outcomes, e->dtype == QE_F32 ? "float32" : "float64", (int)e->A);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t cells = (size_t)P.runs * (size_t)P.S * (size_t)e->ld;
+    hipError_t err;
+    if (outcomes > 1) {  // (the new buffers first: a failed allocation leaves the model as it was)
+        DevBuf<uint32_t> cnt;
+        DevBuf<uint2> key;
+        err = cnt.ensure(cells * (size_t)outcomes);
+        if (err == hipSuccess) err = key.ensure(cells * (size_t)outcomes);
+        if (err == hipSuccess) {
+            P.dyna.ocnt.release();
+            P.dyna.okey.release();
+            P.dyna.entry.release();
+            P.dyna.ocnt = cnt;
+            P.dyna.okey = key;
+        } else {
+            cnt.release();
+            key.release();
+        }
+    } else {
+        err = P.dyna.entry.ensure(cells);
+        if (err == hipSuccess) {
+            P.dyna.ocnt.release();
+            P.dyna.okey.release();
+        }
+    }
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        return qe_fail(err == hipErrorOutOfMemory ? QE_ERR_OOM : QE_ERR_NO_DEVICE, "model_outcomes: the model could not be allocated: %s",
+                       hipGetErrorString(err));
+    }
+    P.dyna.outcomes = outcomes;
+    return model_clear(e);  // another K: the model is forgotten
+}
+
+int qe_population_model_outcomes(qe_engine* e) {
+    if (int rc = need_population(e)) return rc;
+    return e->pop.dyna.outcomes;
+}
+
+int qe_population_outcome_model(qe_engine* e, int32_t* next_states, float* rewards, uint8_t* terminated, uint32_t* counts, int32_t* visited,
+                                int32_t* count) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    if (P.dyna.outcomes < 2)
+        return qe_fail(QE_ERR_INVALID, "the model keeps one outcome per cell: read it with qe_population_model (qe_population_set_model_outcomes)");
+    const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld, K = (size_t)P.dyna.outcomes;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int32_t> hc(m);
+    HIP_TRY(hipMemcpyAsync(hc.data(), P.dyna.count.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (next_states || rewards || terminated || counts) {
+        std::vector<uint2> hk(m * S * ld * K);
+        std::vector<uint32_t> hn(m * S * ld * K);
+        HIP_TRY(hipMemcpyAsync(hk.data(), P.dyna.okey.p, hk.size() * sizeof(uint2), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipMemcpyAsync(hn.data(), P.dyna.ocnt.p, hn.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t r = 0; r < m; ++r)
+            for (size_t s = 0; s < S; ++s)
+                for (size_t a = 0; a < A; ++a)
+                    for (size_t j = 0; j < K; ++j) {
+                        const size_t from = ((r * S + s) * ld + a) * K + j, at = ((r * S + s) * A + a) * K + j;
+                        const bool held = hn[from] != 0u;  // a free slot reads -1, 0.0f, 0, 0
+                        if (next_states) next_states[at] = held ? (int32_t)(hk[from].x & 0x7FFFFFFFu) : -1;
+                        if (rewards) {
+                            const uint32_t bits = held ? hk[from].y : 0u;
+                            memcpy(&rewards[at], &bits, sizeof bits);
+                        }
+                        if (terminated) terminated[at] = held && (hk[from].x >> 31) ? 1 : 0;
+                        if (counts) counts[at] = hn[from];
+                    }
+    }
+    if (visited) {
+        std::vector<int32_t> hv(m * S * A);
+        HIP_TRY(hipMemcpyAsync(hv.data(), P.dyna.visited.p, hv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (size_t r = 0; r < m; ++r)  // table offsets s * ld + a -> cells s * A + a; -1 past the count
+            for (size_t j = 0; j < S * A; ++j) {
+                const int32_t o = hv[r * S * A + j];
+                visited[r * S * A + j] = j < (size_t)hc[r] ? (int32_t)((size_t)o / ld * A + (size_t)o % ld) : -1;
+            }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (count) std::copy(hc.begin(), hc.end(), count);
+    return QE_OK;
+}
+
+int qe_population_set_outcome_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
+                                    const uint32_t* counts, const int32_t* visited, const int32_t* count) {
+    if (int rc = need_population(e)) return rc;
+    PopState& P = e->pop;
+    if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "planning is off (qe_population_set_planning)");
+    if (P.dyna.outcomes < 2)
+        return qe_fail(QE_ERR_INVALID, "the model keeps one outcome per cell: set it with qe_population_set_model (qe_population_set_model_outcomes)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!next_states && !rewards && !terminated && !counts && !visited && !count) return model_clear(e);
+    if (!next_states || !rewards || !terminated || !counts || !visited || !count)
+        return qe_fail(QE_ERR_INVALID, "next_states, rewards, terminated, counts, visited or count is NULL");
+    const size_t m = (size_t)P.runs, S = (size_t)P.S, A = (size_t)e->A, ld = (size_t)e->ld, K = (size_t)P.dyna.outcomes;
+    std::vector<uint2> hk(m * S * ld * K, make_uint2(0u, 0u));
+    std::vector<uint32_t> hn(m * S * ld * K, 0u);
+    std::vector<int32_t> hv(m * S * A, 0);
+    std::vector<uint8_t> listed(S * A);
+    for (size_t r = 0; r < m; ++r) {  // (the kernel indexes the run's table with the keys and the list, and walks the counts)
+        size_t seen = 0;
+        for (size_t c = 0; c < S * A; ++c) {
+            const size_t at = (r * S * A + c) * K, to = ((r * S + c / A) * ld + c % A) * K;
+            unsigned long long total = 0;
+            bool open = false;  // a free slot has been passed
+            for (size_t j = 0; j < K; ++j) {
+                const int32_t p = next_states[at + j];
+                const uint32_t n = counts[at + j];
+                if (p == -1) {
+                    if (n != 0u)
+                        return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld, slot %d: a free slot (next state -1) has count %u", (long long)r,
+                                       (long long)c, (int)j, (unsigned)n);
+                    open = true;
+                    continue;
+                }
+                if (p < 0 || (size_t)p >= S)
+                    return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld, slot %d: next state %d is outside [0, %lld) and is not -1",
+                                   (long long)r, (long long)c, (int)j, (int)p, (long long)S);
+                if (open)
+                    return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld, slot %d: an occupied slot follows a free one", (long long)r,
+                                   (long long)c, (int)j);
+                if (n == 0u)
+                    return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld, slot %d: an occupied slot has count 0", (long long)r, (long long)c,
+                                   (int)j);
+                uint32_t bits;
+                memcpy(&bits, &rewards[at + j], sizeof bits);
+                const uint2 k = make_uint2((uint32_t)p | (terminated[at + j] ? 0x80000000u : 0u), bits);
+                for (size_t i = 0; i < j; ++i) {  // the match rule of the learn step: no outcome is held twice
+                    const uint2 o = hk[to + i];
+                    if (o.y == k.y && (o.x >> 31) == (k.x >> 31) && ((k.x >> 31) || o.x == k.x))
+                        return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld: slots %d and %d hold the same outcome", (long long)r,
+                                       (long long)c, (int)i, (int)j);
+                }
+                hk[to + j] = k;
+                hn[to + j] = n;
+                total += n;
+            }
+            if (total > 0xFFFFFFFFull)
+                return qe_fail(QE_ERR_INVALID, "model of run %lld, cell %lld: the counts add up to %llu, above 2^32 - 1", (long long)r, (long long)c,
+                               total);
+            if (total) ++seen;
+        }
+        if (count[r] < 0 || (size_t)count[r] != seen)
+            return qe_fail(QE_ERR_INVALID, "model of run %lld: count is %d, the model holds %lld seen cells", (long long)r, (int)count[r],
+                           (long long)seen);
+        std::fill(listed.begin(), listed.end(), 0);
+        for (size_t j = 0; j < seen; ++j) {
+            const int32_t c = visited[r * S * A + j];
+            if (c < 0 || (size_t)c >= S * A)
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is outside [0, %lld)", (long long)r,
+                               (long long)j, (int)c, (long long)(S * A));
+            if (next_states[(r * S * A + (size_t)c) * K] == -1)
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is unseen in the model", (long long)r,
+                               (long long)j, (int)c);
+            if (listed[(size_t)c])
+                return qe_fail(QE_ERR_INVALID, "visited list of run %lld, entry %lld: cell %d is listed twice", (long long)r, (long long)j,
+                               (int)c);
+            listed[(size_t)c] = 1;
+            hv[r * S * A + j] = (int32_t)((size_t)c / A * ld + (size_t)c % A);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(P.dyna.okey.p, hk.data(), hk.size() * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.ocnt.p, hn.data(), hn.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.visited.p, hv.data(), hv.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(P.dyna.count.p, count, m * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return QE_OK;
+}
+
 int qe_population_set_sweeping(qe_engine* e, int32_t queue_length, const double* thresholds) {
     if (int rc = need_population(e)) return rc;
     PopState& P = e->pop;
@@ -1227,6 +1442,11 @@ int qe_population_set_sweeping(qe_engine* e, int32_t queue_length, const double*
         return QE_OK;
     }
     if (!P.dyna.planning) return qe_fail(QE_ERR_INVALID, "prioritized sweeping orders the planning updates: planning is off (qe_population_set_planning)");
+    if (P.dyna.outcomes > 1)
+        return qe_fail(QE_ERR_UNSUPPORTED,
+                       "prioritized sweeping: the model keeps %d outcomes per cell, and sweeping over a sample model needs expected "
+                       "updates, which are not built (qe_population_set_model_outcomes)",
+                       P.dyna.outcomes);
     if (!thresholds) return qe_fail(QE_ERR_INVALID, "thresholds is NULL");
     const size_t m = (size_t)P.runs;
     for (size_t r = 0; r < m; ++r)

@@ -104,7 +104,9 @@ typedef struct qe_rollout_stats {
                                 population with Dyna-Q (qe_population_set_planning): NV and masked as path 6, and the
                                 planning updates per step in bits 24-30 -- with bit 4 set the planning order is
                                 prioritized sweeping (qe_population_set_sweeping) and bits 5-9 hold its queue length
-                                minus 1 --; path 14: population with visit counts
+                                minus 1; with bits 21-23 non-zero the model is the sample model
+                                (qe_population_set_model_outcomes) and they hold its slots per cell minus 1, bits no
+                                other path uses --; path 14: population with visit counts
                                 (qe_population_set_visits): NV and masked as path 6, visit_lr in bit 4 and "some run's
                                 beta is above 0" in bit 5; path 15: population with n-step Tree Backup
                                 (qe_population_set_tree_backup): NV and masked as path 6, and n in bits 24-28 */
@@ -451,6 +453,32 @@ int qe_delta_apply_gathered_dev(qe_engine* e, const void* gathered_dev, int64_t 
  *                         unseen in the model or listed twice; entries from count on and the rewards and flags of unseen
  *                         cells are not read.  While sweeping is on (below) the upload also rebuilds every predecessor
  *                         list in its canonical order and empties every queue.
+ *   qe_population_set_model_outcomes  the sample model of Sutton & Barto ch. 8 for stochastic environments: K slots per cell,
+ *                         K in 1 .. 8; 1 (the default) is the last-outcome model above.  It needs planning on.  K > 1: every
+ *                         cell keeps up to K distinct outcomes (next_obs, reward, terminated) with a uint32 count each;
+ *                         occupied slots form a prefix in order of first observation, and a cell is seen when slot 0 is
+ *                         occupied.  Learning (s', r, terminated) of (s, a): a slot MATCHES when its reward has the same 32
+ *                         bits, its flag is the same, and the flag is set or its next_obs is s'.  On a match the slot's
+ *                         next_obs becomes s' and its count goes up by one unless the cell's total N (the sum of its
+ *                         counts) is 2^32 - 1; else the first free slot, or with none free the slot with the smallest count
+ *                         (the lowest index among equals), becomes (s', r, terminated, 1).  Planning update i draws c_i as
+ *                         above, then y_i = word i & 3 of the Philox block (agent id, k_lo, k_hi, 3 | (i >> 2) << 8),
+ *                         t = mulhi32(y_i, N(c_i)), and takes (p, rho, tau) from the first slot j with t < n_0 + .. + n_j;
+ *                         the rest is the update above.  Changing K forgets the model, setting the same K keeps it, and
+ *                         turning planning off frees it (K is 1 again).  QE_ERR_INVALID: not a population engine, K out of
+ *                         range or planning off; QE_ERR_UNSUPPORTED: K > 1 while sweeping is on (sweeping over a sample
+ *                         model needs expected updates, which are not built; qe_population_set_sweeping is refused likewise
+ *                         while K > 1), or a (dtype, row stride) whose kernel is not built.
+ *   qe_population_model_outcomes  K (or a negative qe_status).
+ *   qe_population_outcome_model / qe_population_set_outcome_model  the sample model (K > 1) and the list: next_states,
+ *                         rewards, terminated and counts hold runs * S * A * K entries, slot j of run r's cell c at
+ *                         [(r * S * A + c) * K + j]; a free slot reads -1, 0.0f, 0, 0; visited and count as above.  The
+ *                         upload takes all six, or all NULL: every run forgets everything.  It refuses (QE_ERR_INVALID, and
+ *                         nothing changes) what the checks above refuse and: an occupied slot behind a free one, an
+ *                         occupied slot with count 0 or a free one with another count, two slots of a cell that match each
+ *                         other, and a cell whose counts add up to more than 2^32 - 1.  While K > 1, qe_population_model
+ *                         returns QE_ERR_UNSUPPORTED (read the model here) and qe_population_set_model loads its
+ *                         last-outcome model as slot 0 with count 1.  QE_ERR_INVALID while planning is off or K is 1.
  *   qe_population_set_sweeping  prioritized sweeping (Moore & Atkeson 1993; Sutton & Barto 8.4) as the order of the planning
  *                         updates: queue_length slots per run, 1 .. 32, and every run's threshold theta (finite, >= 0);
  *                         queue_length 0 (thresholds ignored) turns it off, frees the index and the queues, and gives
@@ -565,6 +593,12 @@ int qe_population_model(qe_engine* e, int32_t* next_states, float* rewards, uint
                         int32_t* count);
 int qe_population_set_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
                             const int32_t* visited, const int32_t* count);
+int qe_population_set_model_outcomes(qe_engine* e, int32_t model_outcomes);
+int qe_population_model_outcomes(qe_engine* e);
+int qe_population_outcome_model(qe_engine* e, int32_t* next_states, float* rewards, uint8_t* terminated, uint32_t* counts,
+                                int32_t* visited, int32_t* count);
+int qe_population_set_outcome_model(qe_engine* e, const int32_t* next_states, const float* rewards, const uint8_t* terminated,
+                                    const uint32_t* counts, const int32_t* visited, const int32_t* count);
 int qe_population_set_sweeping(qe_engine* e, int32_t queue_length, const double* thresholds /* [runs] */);
 int qe_population_sweeping(qe_engine* e);
 int qe_population_predecessors(qe_engine* e, int32_t* head, int32_t* next);
